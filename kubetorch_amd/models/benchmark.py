@@ -19,12 +19,45 @@ def _log(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
+DUMP_SAMPLE_SEED = 20240229
+DUMP_SAMPLE_ELEMS = 1 << 20  # 4 MiB of fp32, far under 64 MB
+
+
+def _dump_outputs(out_dir, loss, engine):
+    """Write what the last timed step handed back to its caller as
+    <out_dir>/<name>.npy (fp32): the loss it returned, and a fixed seeded
+    sample of the state it left behind in the engine, the parameters
+    after its AdamW update (~16 GB in full for the 8B model). Sample
+    positions depend only on the bucket layout, so two builds run with
+    the same arguments dump the same elements."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().reshape(1).cpu().numpy())
+    gen = torch.Generator(device="cpu").manual_seed(DUMP_SAMPLE_SEED)
+    per_bucket = max(1, DUMP_SAMPLE_ELEMS // len(engine.buckets))
+    params = []
+    for b in engine.buckets:
+        if b.numel <= per_bucket:
+            idx = torch.arange(b.numel)
+        else:
+            idx = torch.randint(0, b.numel, (per_bucket,), generator=gen)
+        idx = idx.to(b.flat_param.device)
+        params.append(b.flat_param[idx].float().cpu())
+    np.save(os.path.join(out_dir, "params_sample.npy"),
+            torch.cat(params).numpy())
+
+
 def run_training_benchmark(steps=8, warmup=3, batch=4, seq=4096,
                            model="llama3-8b", bucket_mb=256, zero=False,
                            lr=1e-4, sdpa="efficient", ckpt=False,
-                           profile=False, expected_gpus=None):
+                           profile=False, expected_gpus=None,
+                           dump_outputs=None):
     """One full benchmark run on this rank. Returns the result dict on
-    rank 0, None on other ranks. Weak scaling: per-GPU batch is fixed."""
+    rank 0, None on other ranks. Weak scaling: per-GPU batch is fixed.
+    dump_outputs: directory rank 0 writes the last timed step's outputs
+    to after the timed region (see _dump_outputs)."""
     from kubetorch_amd.models import Llama, llama3_8b, llama_tiny
     from kubetorch_amd.parallel import FlatDDP, init_distributed
 
@@ -109,10 +142,14 @@ def run_training_benchmark(steps=8, warmup=3, batch=4, seq=4096,
 
     barrier_sync()
     t0 = time.perf_counter()
+    loss = None
     for _ in range(steps):
-        one_step()
+        loss = one_step()
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if dump_outputs and rank == 0 and loss is not None:
+        _dump_outputs(dump_outputs, loss, engine)
 
     # MAX over ranks
     t = torch.tensor([elapsed], dtype=torch.float64,

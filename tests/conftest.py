@@ -5,11 +5,49 @@ tests automatically when no GPU is present, mirroring the reference's
 level system (reference: python_client/tests/conftest.py:27-41).
 """
 import os
+import shutil
 import sys
+import tempfile
 
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+# The package keeps pod logs, local volumes and secrets, the localfs
+# registry and the GPU data server's socket and lock under fixed names in
+# the system temp directory, and its store under the home directory. On a
+# shared host those names may already belong to another user (open() and
+# remove() then fail with EACCES), so the suite runs in a private temp
+# directory of its own: set before any kubetorch_amd import reads the
+# paths, and inherited through the environment by the pods and daemons
+# that tests start. pytest's own tmp_path root stays where it was.
+# The directory sits directly under /tmp where that is writable, whatever
+# TMPDIR says, to keep the unix socket paths below it short (see sock_dir).
+_SYSTEM_TMP = tempfile.gettempdir()
+_SUITE_TMP = tempfile.mkdtemp(
+    prefix="kt-", dir="/tmp" if os.access("/tmp", os.W_OK | os.X_OK) else None)
+os.environ.setdefault("PYTEST_DEBUG_TEMPROOT", _SYSTEM_TMP)
+os.environ["TMPDIR"] = _SUITE_TMP
+tempfile.tempdir = _SUITE_TMP
+os.environ.setdefault("KT_GPU_DATA_SOCK",
+                      os.path.join(_SUITE_TMP, "kt-amd-gpu-data.sock"))
+os.environ.setdefault("KT_STORE_ROOT", os.path.join(_SUITE_TMP, "store"))
+
+
+def pytest_unconfigure(config):
+    shutil.rmtree(_SUITE_TMP, ignore_errors=True)
+
+
+@pytest.fixture()
+def sock_dir():
+    """A short private directory for unix sockets. sockaddr_un.sun_path
+    holds 107 bytes, and tmp_path (temp root + user name + test name) can
+    be longer than that: bind() then fails and the pod-data-server never
+    comes up. The directory lives until the session ends (a client built
+    with the default socket path keeps the one it first saw); removing
+    the suite's temp directory then also ends the daemons serving in it
+    (they exit once their socket file is gone)."""
+    return tempfile.mkdtemp(prefix="s-", dir=_SUITE_TMP)
 
 
 def pytest_addoption(parser):

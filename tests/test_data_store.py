@@ -121,8 +121,8 @@ def test_file_store_http_server(tmp_store):
 
 class TestTensorStore:
     @pytest.fixture()
-    def pd_env(self, tmp_path, monkeypatch):
-        sock = str(tmp_path / "pd.sock")
+    def pd_env(self, tmp_path, sock_dir, monkeypatch):
+        sock = os.path.join(sock_dir, "pd.sock")
         monkeypatch.setenv("KT_GPU_DATA_SOCK", sock)
         monkeypatch.setenv("KT_STORE_ROOT", str(tmp_path / "store"))
         monkeypatch.delenv("KT_STORE_URL", raising=False)
@@ -166,7 +166,7 @@ class TestTensorStore:
         gpu_store.get("ckpt2", dest)
         torch.testing.assert_close(dest["y"], sd["y"])
 
-    def test_cross_server_broadcast_cpu(self, pd_env, tmp_path):
+    def test_cross_server_broadcast_cpu(self, pd_env, sock_dir):
         """Two daemons on localhost = two 'nodes'; transfer via a 2-rank
         gloo process group (the RCCL path on GPU nodes)."""
         from kubetorch_amd.data_store.pod_data_server import (
@@ -174,7 +174,7 @@ class TestTensorStore:
             ensure_server,
         )
 
-        sock_a = str(tmp_path / "a.sock")
+        sock_a = os.path.join(sock_dir, "a.sock")
         sock_b = pd_env
         port_a = _free_port()
         ensure_server(sock_a, tcp_port=port_a)
@@ -224,10 +224,10 @@ def _gpu_putter(sock, q):
 
 
 @pytest.mark.gpu
-def test_gpu_ipc_put_get(tmp_path):
+def test_gpu_ipc_put_get(tmp_path, sock_dir):
     """Publish a GPU tensor from process A; process B receives it through
     the daemon's hipIpc device-to-device copy (no RCCL on same node)."""
-    sock = str(tmp_path / "gpu_pd.sock")
+    sock = os.path.join(sock_dir, "gpu_pd.sock")
     os.environ["KT_GPU_DATA_SOCK"] = sock
     os.environ["KT_STORE_ROOT"] = str(tmp_path / "store")
     import kubetorch_amd.data_store.pod_data_server as pds
@@ -274,11 +274,11 @@ def _bcast_receiver(sock, store_root, rank_tag, q):
     q.put((rank_tag, dest["w"].sum().item(), dest["b"].sum().item()))
 
 
-def test_three_party_broadcast_cpu(tmp_path, monkeypatch):
+def test_three_party_broadcast_cpu(tmp_path, sock_dir, monkeypatch):
     """1 source + 2 receivers through ONE gloo broadcast group (the RCCL
     path on GPU nodes; BroadcastWindow coordination via the metadata
     layer)."""
-    sock = str(tmp_path / "bc.sock")
+    sock = os.path.join(sock_dir, "bc.sock")
     store_root = str(tmp_path / "store")
     monkeypatch.setenv("KT_GPU_DATA_SOCK", sock)
     monkeypatch.setenv("KT_STORE_ROOT", store_root)
@@ -311,10 +311,10 @@ def test_three_party_broadcast_cpu(tmp_path, monkeypatch):
     gs._client = None
 
 
-def test_daemon_failure_auto_restart(tmp_path, monkeypatch):
+def test_daemon_failure_auto_restart(tmp_path, sock_dir, monkeypatch):
     """Kill the pod-data-server; the client's next request restarts it
     (reference parity: test_gpu_store.py failure injection + auto-restart)."""
-    sock = str(tmp_path / "fi.sock")
+    sock = os.path.join(sock_dir, "fi.sock")
     monkeypatch.setenv("KT_GPU_DATA_SOCK", sock)
     monkeypatch.setenv("KT_STORE_ROOT", str(tmp_path / "store"))
     import kubetorch_amd.data_store.pod_data_server as pds

@@ -296,7 +296,13 @@ class _FusedCE(torch.autograd.Function):
     def backward(ctx, gout):
         dlogits, n_valid = ctx.saved_tensors
         scale = (gout / n_valid).to(torch.float32)
-        return (dlogits * scale).to(dlogits.dtype).reshape(ctx.shape), None, None
+        if dlogits.is_cuda:
+            # a bf16 tensor times a 0-dim GPU tensor would round the factor
+            # itself to bf16; the kernel multiplies in fp32 and rounds once
+            g = _ext().scale_bf16(dlogits, scale.reshape(1))
+        else:
+            g = (dlogits * scale).to(dlogits.dtype)
+        return g.reshape(ctx.shape), None, None
 
 
 def fused_cross_entropy(logits, targets, ignore_index=-100):
@@ -418,6 +424,13 @@ def aligned_offsets(numels, elem_size):
     return offs, cur
 
 
+def _all_aligned(tensors):
+    """The pack kernel copies 16 B vectors from each tensor's data pointer.
+    A contiguous view into the middle of an allocation (t[1:]) need not
+    start on such a boundary; calls holding one take the per-tensor copy."""
+    return all(t.data_ptr() % PACK_ALIGN == 0 for t in tensors)
+
+
 def pack_tensors(tensors, flat=None):
     """Pack same-dtype contiguous GPU tensors into one flat buffer with a
     single kernel (vs torch.cat's per-tensor copies). Returns (flat,
@@ -429,7 +442,8 @@ def pack_tensors(tensors, flat=None):
     dev = tensors[0].device
     if flat is None:
         flat = torch.zeros(total, dtype=dt, device=dev)
-    if dev.type == "cuda" and hip_available():
+    if (dev.type == "cuda" and hip_available()
+            and _all_aligned(list(tensors) + [flat])):
         ptrs = torch.tensor([t.data_ptr() for t in tensors],
                             dtype=torch.int64).to(dev, non_blocking=True)
         nb = torch.tensor([n * es for n in numels],
@@ -451,7 +465,9 @@ def unpack_tensors(flat, tensors, offsets=None):
     if offsets is None:
         offsets, _ = aligned_offsets(numels, es)
     if (flat.is_cuda and hip_available()
-            and all(t.is_contiguous() for t in tensors)):
+            and all(t.is_contiguous() for t in tensors)
+            and all(o * es % PACK_ALIGN == 0 for o in offsets)
+            and _all_aligned(list(tensors) + [flat])):
         dev = flat.device
         ptrs = torch.tensor([t.data_ptr() for t in tensors],
                             dtype=torch.int64).to(dev, non_blocking=True)

@@ -29,6 +29,8 @@ void kt_swiglu_bwd(const void* dout, const void* gu, void* dgu, long N, int I,
 void kt_cross_entropy_fwd(void* logits, const void* targets, void* loss,
                           int N, int V, float scale, long ignore_index,
                           hipStream_t stream);
+void kt_scale_bf16(const void* in, void* out, const void* scale, long n,
+                   hipStream_t stream);
 void kt_adamw(void* p, const void* g, void* m, void* v, long n, float lr,
               float beta1, float beta2, float eps, float wd, float bc1,
               float bc2, float grad_scale, hipStream_t stream);
@@ -102,6 +104,24 @@ std::vector<at::Tensor> rmsnorm_bwd(const at::Tensor& dy,
   CHECK_BF16_CONTIG(w);
   const int H = (int)x.size(-1);
   const long N = x.numel() / H;
+  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
+  TORCH_CHECK(w.numel() == H, "weight shape mismatch");
+  TORCH_CHECK(dy.sizes() == x.sizes(), "dy shape mismatch");
+  TORCH_CHECK(invrms.is_cuda() && invrms.scalar_type() == at::kFloat &&
+                  invrms.is_contiguous() && invrms.numel() == N,
+              "invrms must be N contiguous fp32 values on GPU");
+  // The kernel keeps its dw accumulator in H*4 bytes of dynamic LDS next to
+  // the 64 B static scratch of block_reduce_sum. The limit is read from the
+  // runtime (hipDeviceAttributeMaxSharedMemoryPerBlock of x's device),
+  // the bound the HIP runtime holds a launch's static + dynamic LDS to,
+  // rather than assumed from the size of a CU's LDS.
+  int lds_max = 0;
+  TORCH_CHECK(hipDeviceGetAttribute(&lds_max,
+                                    hipDeviceAttributeMaxSharedMemoryPerBlock,
+                                    x.device().index()) == hipSuccess,
+              "cannot read the LDS limit");
+  TORCH_CHECK((size_t)H * sizeof(float) + 64 <= (size_t)lds_max,
+              "H too large for the rmsnorm_bwd LDS accumulator");
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
   auto dx = at::empty_like(x);
   auto dw = at::empty_like(w);
@@ -110,6 +130,7 @@ std::vector<at::Tensor> rmsnorm_bwd(const at::Tensor& dy,
   const void* ds_ptr = nullptr;
   if (ds.has_value()) {
     CHECK_BF16_CONTIG(ds.value());
+    TORCH_CHECK(ds->sizes() == x.sizes(), "ds shape mismatch");
     ds_ptr = ds->data_ptr();
   }
   kt_rmsnorm_bwd(dy.data_ptr(), ds_ptr, x.data_ptr(), w.data_ptr(),
@@ -158,8 +179,11 @@ at::Tensor swiglu_bwd(const at::Tensor& dout, const at::Tensor& gu) {
   CHECK_BF16_CONTIG(dout);
   CHECK_BF16_CONTIG(gu);
   const int twoI = (int)gu.size(-1);
+  TORCH_CHECK(twoI % 16 == 0, "2*I must be a multiple of 16");
   const int I = twoI / 2;
   const long N = gu.numel() / twoI;
+  TORCH_CHECK(dout.size(-1) == I && dout.numel() == N * I,
+              "dout shape mismatch");
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(gu.device());
   auto dgu = at::empty_like(gu);
   kt_swiglu_bwd(dout.data_ptr(), gu.data_ptr(), dgu.data_ptr(), N, I,
@@ -181,6 +205,22 @@ at::Tensor cross_entropy_fwd_(at::Tensor logits, const at::Tensor& targets,
                        (int)N, V, (float)scale, ignore_index,
                        cur_stream(logits));
   return loss;
+}
+
+at::Tensor scale_bf16(const at::Tensor& x, const at::Tensor& scale) {
+  // bf16(x * scale) with the fp32 scale read from device memory (no sync,
+  // no rounding of the factor to bf16).
+  CHECK_BF16_CONTIG(x);
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat &&
+                  scale.numel() == 1 && scale.device() == x.device(),
+              "scale must be one fp32 value on x's device");
+  TORCH_CHECK(x.numel() % 8 == 0, "numel must be a multiple of 8");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  auto out = at::empty_like(x);
+  if (x.numel() > 0)
+    kt_scale_bf16(x.data_ptr(), out.data_ptr(), scale.data_ptr(), x.numel(),
+                  cur_stream(x));
+  return out;
 }
 
 void adamw_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v,
@@ -384,6 +424,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward (bf16)");
   mod.def("cross_entropy_fwd_", &cross_entropy_fwd_,
           "Fused CE: returns per-row loss, overwrites logits with grad");
+  mod.def("scale_bf16", &scale_bf16,
+          "bf16(x * scale), scale one fp32 value in device memory");
   mod.def("adamw_", &adamw_, "Fused AdamW on a flat bf16 bucket");
   mod.def("pack_segments", &pack_segments,
           "One-kernel multi-tensor pack/unpack vs a flat buffer");

@@ -110,7 +110,8 @@ __global__ void rmsnorm_fwd_kernel(const u16* __restrict__ x,
 //   dx_i = ir*(dy_i*w_i) - x_i * ir^3/H * S,  S = sum_j dy_j*w_j*x_j
 //   dw_j = sum_rows dy_j * x_j * ir   (accumulated per-block in LDS, written
 //          to a [gridDim.x, H] fp32 partial buffer; reduced by colsum below)
-// LDS budget: H fp32 <= 160KB -> H <= 40960 (Llama H=4096 -> 16 KB). Fine.
+// LDS budget: H fp32 of dynamic LDS (Llama H=4096 -> 16 KB); the binding
+// checks it against the device's per-block limit before the launch.
 // ---------------------------------------------------------------------------
 // ds (nullable): upstream gradient of the summed residual stream s (fused
 // path) — added into dx, so dx = ds + d(norm)/ds·dy, which is the gradient
@@ -337,7 +338,9 @@ __global__ void cross_entropy_fwd_kernel(u16* __restrict__ logits,
       __syncthreads();
       continue;
     }
-    // pass 1: thread-local online max + sumexp
+    // pass 1: thread-local online max + sumexp. A -inf logit (masked
+    // vocabulary) adds nothing; seen before any finite one it must not
+    // compute exp(-inf - -inf) = NaN, same as the wave merge below.
     float m = -INFINITY, s = 0.f;
     for (int vI = threadIdx.x; vI < nvec; vI += blockDim.x) {
       vec8u xv = *reinterpret_cast<const vec8u*>(lr + vI * 8);
@@ -347,7 +350,7 @@ __global__ void cross_entropy_fwd_kernel(u16* __restrict__ logits,
         if (f > m) {
           s = s * __expf(m - f) + 1.f;
           m = f;
-        } else {
+        } else if (f > -INFINITY) {
           s += __expf(f - m);
         }
       }
@@ -390,6 +393,24 @@ __global__ void cross_entropy_fwd_kernel(u16* __restrict__ logits,
       *reinterpret_cast<vec8u*>(lr + vI * 8) = ov;
     }
     __syncthreads();
+  }
+}
+
+// out = bf16(in * *scale), the scale an fp32 value in device memory. The
+// cross-entropy backward scales the stored gradient by gout / n_valid, both
+// device scalars: a torch bf16-tensor * 0-dim-GPU-tensor product rounds that
+// factor to bf16 first (off by up to 2^-9 when n_valid is no power of two).
+__global__ void scale_bf16_kernel(const u16* __restrict__ in,
+                                  u16* __restrict__ out,
+                                  const float* __restrict__ scale, long nvec) {
+  const float sc = *scale;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < nvec;
+       t += (long)gridDim.x * blockDim.x) {
+    vec8u xv = *reinterpret_cast<const vec8u*>(in + t * 8);
+    vec8u ov;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ov[j] = f2bf(bf2f(xv[j]) * sc);
+    *reinterpret_cast<vec8u*>(out + t * 8) = ov;
   }
 }
 
@@ -477,7 +498,8 @@ __global__ void pack_segments_kernel(const unsigned long long* __restrict__ ptrs
   const int seg = blockIdx.y;
   const long B = nbytes[seg];
   char* flat = base + offs[seg];                       // 16 B aligned
-  char* t = reinterpret_cast<char*>(ptrs[seg]);        // torch alloc: aligned
+  char* t = reinterpret_cast<char*>(ptrs[seg]);        // 16 B aligned: host
+                                                       // checks data_ptr()
   char* dst = to_base ? flat : t;
   const char* src = to_base ? (const char*)t : (const char*)flat;
   const long nvec = B >> 4;
@@ -558,6 +580,14 @@ void kt_cross_entropy_fwd(void* logits, const void* targets, void* loss, int N,
   hipLaunchKernelGGL(cross_entropy_fwd_kernel, dim3(grid), dim3(256), 0,
                      stream, (u16*)logits, (const long*)targets, (float*)loss,
                      N, V, scale, ignore_index);
+}
+
+void kt_scale_bf16(const void* in, void* out, const void* scale, long n,
+                   hipStream_t stream) {
+  long nvec = n >> 3;  // host checks n % 8 == 0
+  int grid = grid_for(nvec, 256);
+  hipLaunchKernelGGL(scale_bf16_kernel, dim3(grid), dim3(256), 0, stream,
+                     (const u16*)in, (u16*)out, (const float*)scale, nvec);
 }
 
 void kt_adamw(void* p, const void* g, void* m, void* v, long n, float lr,

@@ -8,4 +8,5 @@ from kubetorch_amd.models.llama import (  # noqa: F401
     llama_tiny,
 )
 from kubetorch_amd.models.moe import MoEMLP, convert_to_moe  # noqa: F401
+from kubetorch_amd.models.paged_kv import PagedKVCache  # noqa: F401
 from kubetorch_amd.models.serving import BatchedGenerator  # noqa: F401

@@ -11,6 +11,12 @@ Per-slot positions make the stock forward unusable (RoPE offset and the
 causal horizon differ per row), so the decode step is written against the
 same ops the model uses (rmsnorm/swiglu kernels, SDPA with a length mask),
 keeping numerics aligned with `Llama.generate`.
+
+`kv="paged"` (opt-in) replaces the slot slabs with a block-table paged
+cache (models/paged_kv.py): pages for prompt + max_new_tokens are reserved
+at admission, new k/v are scattered into pages and attention runs the
+paged decode kernel (ops.paged_attention_decode), whose reads follow each
+sequence's own length; one captured graph serves every horizon.
 """
 from dataclasses import dataclass, field
 
@@ -32,7 +38,10 @@ class _Request:
 
 class BatchedGenerator:
     def __init__(self, model, max_batch=8, max_len=None, device=None,
-                 prefill_chunk=None, graph=None):
+                 prefill_chunk=None, graph=None, kv="slot", page_size=16,
+                 num_pages=None, num_splits=None):
+        if kv not in ("slot", "paged"):
+            raise ValueError(f"kv must be 'slot' or 'paged', got {kv!r}")
         self.model = model
         cfg = model.cfg
         self.cfg = cfg
@@ -42,11 +51,29 @@ class BatchedGenerator:
         p = next(model.parameters())
         self.device = device or p.device
         self.dtype = p.dtype
-        shape = (max_batch, cfg.n_kv_heads, self.max_len, cfg.head_dim)
-        self.k = [torch.zeros(shape, device=self.device, dtype=self.dtype)
-                  for _ in range(cfg.n_layers)]
-        self.v = [torch.zeros(shape, device=self.device, dtype=self.dtype)
-                  for _ in range(cfg.n_layers)]
+        self._paged = kv == "paged"
+        if self._paged:
+            # kv="paged": block-table page pools (models/paged_kv.py) and
+            # the paged HIP kernels; no slot slabs are allocated. The
+            # default pool has the slot cache's capacity, so admission
+            # never waits for pages; a smaller num_pages makes it wait.
+            from kubetorch_amd.models.paged_kv import PagedKVCache
+
+            max_blocks = -(-self.max_len // page_size)
+            if num_pages is None:
+                num_pages = max_batch * max_blocks
+            self._pkv = PagedKVCache(cfg, num_pages, page_size, max_batch,
+                                     max_blocks, self.device, self.dtype)
+            # fixed for the engine's life so the decode grid is static
+            # (one captured graph serves every horizon)
+            self._num_splits = num_splits or ops.paged_num_splits(
+                max_batch, cfg.n_kv_heads, max_blocks * page_size)
+        else:
+            shape = (max_batch, cfg.n_kv_heads, self.max_len, cfg.head_dim)
+            self.k = [torch.zeros(shape, device=self.device, dtype=self.dtype)
+                      for _ in range(cfg.n_layers)]
+            self.v = [torch.zeros(shape, device=self.device, dtype=self.dtype)
+                      for _ in range(cfg.n_layers)]
         self.lens = torch.zeros(max_batch, dtype=torch.long, device=self.device)
         self.slots = [None] * max_batch   # slot -> _Request
         self.pending = []
@@ -85,6 +112,9 @@ class BatchedGenerator:
                                  device=self.device).reshape(-1)
         if prompt.numel() + max_new_tokens > self.max_len:
             raise ValueError("prompt + max_new_tokens exceeds max_len")
+        if self._paged and self._pkv.pages_needed(
+                prompt.numel() + max_new_tokens) > self._pkv.num_pages:
+            raise ValueError("request needs more pages than the pool holds")
         self.pending.append(_Request(rid, prompt, max_new_tokens,
                                      temperature, stop_token))
         return rid
@@ -109,6 +139,13 @@ class BatchedGenerator:
         admitted = []
         for slot in range(self.max_batch):
             if self.slots[slot] is None and self.pending:
+                if self._paged:
+                    # FIFO: if the head does not fit, it and everything
+                    # behind it wait for pages freed by a later finish
+                    head = self.pending[0]
+                    if not self._pkv.reserve(
+                            slot, head.prompt.numel() + head.max_new_tokens):
+                        break
                 req = self.pending.pop(0)
                 req.slot = slot
                 self.slots[slot] = req
@@ -139,9 +176,7 @@ class BatchedGenerator:
         cache = KVCache(self.cfg, G, S0, self.device, self.dtype)
         logits = self.model._forward_cached(batch, cache)
         for j, req in enumerate(group):
-            for i in range(self.cfg.n_layers):
-                self.k[i][req.slot, :, :S0] = cache.k[i][j, :, :S0]
-                self.v[i][req.slot, :, :S0] = cache.v[i][j, :, :S0]
+            self._store_prefill(req, cache, j, S0)
             self.lens[req.slot] = S0
             self._host_lens[req.slot] = S0
             req.out = req.prompt.tolist()
@@ -161,13 +196,31 @@ class BatchedGenerator:
                     req.prompt[s0:s0 + pc].view(1, -1), cache)
         else:
             logits = self.model._forward_cached(req.prompt.view(1, -1), cache)
-        for i in range(self.cfg.n_layers):
-            self.k[i][req.slot, :, :S0] = cache.k[i][0, :, :S0]
-            self.v[i][req.slot, :, :S0] = cache.v[i][0, :, :S0]
+        self._store_prefill(req, cache, 0, S0)
         self.lens[req.slot] = S0
         self._host_lens[req.slot] = S0
         req.out = req.prompt.tolist()
         self._emit(req, logits[0])
+
+    def _store_prefill(self, req, cache, j, S0):
+        """Move row j of a prefill cache into the request's slot (slot
+        mode) or scatter it into the slot's pages (paged mode: one
+        paged_kv_write per layer)."""
+        if not self._paged:
+            for i in range(self.cfg.n_layers):
+                self.k[i][req.slot, :, :S0] = cache.k[i][j, :, :S0]
+                self.v[i][req.slot, :, :S0] = cache.v[i][j, :, :S0]
+            return
+        ps = self._pkv.page_size
+        pages = self._pkv.pages_of(req.slot)
+        slot_map = torch.tensor(
+            [pages[t // ps] * ps + t % ps for t in range(S0)],
+            dtype=torch.int32).to(self.device)
+        for i in range(self.cfg.n_layers):
+            # [n_kv, S0, hd] -> [S0, n_kv, hd] views, no copy
+            ops.paged_kv_write(cache.k[i][j, :, :S0].transpose(0, 1),
+                               cache.v[i][j, :, :S0].transpose(0, 1),
+                               self._pkv.k[i], self._pkv.v[i], slot_map)
 
     def _sample(self, req, logits):
         if req.temperature > 0:
@@ -186,6 +239,8 @@ class BatchedGenerator:
             self.slots[req.slot] = None
             self.lens[req.slot] = 0
             self._host_lens[req.slot] = 0
+            if self._paged:
+                self._pkv.release(req.slot)
 
     def _decode(self, active):
         if self._use_graph:
@@ -229,6 +284,50 @@ class BatchedGenerator:
         self.lens.add_(self._g_act)  # active slots advance one position
         return logits
 
+    def _paged_math(self, toks, lens, act, table):
+        """One decode step over the paged cache for the rows given (all
+        slots under a graph, the active ones in eager mode): same math as
+        the slot step, but new k/v go to their pages with paged_kv_write
+        and attention is ops.paged_attention_decode, which reads lengths
+        and tables from device buffers. No mask tensor, no horizon slice,
+        no host sync. Rows with act == 0 write nothing (negative slot) and
+        attend over nothing (length 0, zero output)."""
+        cfg, m = self.cfg, self.model
+        B = toks.shape[0]
+        hd, Hq, Hkv = cfg.head_dim, cfg.n_heads, cfg.n_kv_heads
+        eps = cfg.norm_eps
+        ps = self._pkv.page_size
+        cos = m.rope_cos[lens].view(B, 1, 1, hd // 2)
+        sin = m.rope_sin[lens].view(B, 1, 1, hd // 2)
+        blk = (lens // ps).clamp(max=self._pkv.max_blocks - 1)
+        page = table.gather(1, blk.view(B, 1)).view(B).long()
+        live = (act > 0) & (page >= 0)
+        slot_map = torch.where(live, page * ps + lens % ps,
+                               torch.full_like(page, -1)).to(torch.int32)
+        seq_lens = ((lens + 1) * act).to(torch.int32)
+        h = m.embed(toks).view(B, 1, cfg.dim)
+        for i, layer in enumerate(m.layers):
+            n1 = ops.rmsnorm(h, layer.attn_norm.weight, eps)
+            qkv = layer.attn.wqkv(n1)
+            q, k, v = qkv.split([Hq * hd, Hkv * hd, Hkv * hd], dim=-1)
+            q = self._rope1(q.view(B, 1, Hq, hd), cos, sin)
+            k = self._rope1(k.view(B, 1, Hkv, hd), cos, sin)
+            v = v.view(B, 1, Hkv, hd)
+            kp, vp = self._pkv.k[i], self._pkv.v[i]
+            ops.paged_kv_write(k[:, 0], v[:, 0], kp, vp, slot_map)
+            o = ops.paged_attention_decode(q[:, 0], kp, vp, table, seq_lens,
+                                           num_splits=self._num_splits)
+            h = h + layer.attn.wo(o.reshape(B, 1, -1))
+            n2 = ops.rmsnorm(h, layer.mlp_norm.weight, eps)
+            h = h + layer.mlp(n2)
+        return m.lm_head(ops.rmsnorm(h, m.norm.weight, eps))[:, -1]
+
+    def _decode_math_paged(self):
+        logits = self._paged_math(self._g_toks, self.lens, self._g_act,
+                                  self._pkv.block_table)
+        self.lens.add_(self._g_act)  # active slots advance one position
+        return logits
+
     def _bucket_for(self, need):
         """Smallest power-of-two horizon >= need (>=128), capped at
         max_len. The per-bucket graphs keep attention reads proportional
@@ -249,19 +348,26 @@ class BatchedGenerator:
                                       device=self.device)
             self._g_pool = torch.cuda.graph_pool_handle()
         lens_snapshot = self.lens.clone()
+        math = (self._decode_math_paged if self._paged
+                else lambda: self._decode_math(L))
         for _ in range(2):  # warm up allocator/workspaces pre-capture
-            self._decode_math(L)
+            math()
         self.lens.copy_(lens_snapshot)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, pool=self._g_pool):
-            logits = self._decode_math(L)
+            logits = math()
         self._graphs[L] = (graph, logits)
         return self._graphs[L]
 
     def _decode_graph(self, active):
-        need = max(self._host_lens[s] for s in active) + 1
-        graph, logits = self._ensure_graph(self._bucket_for(need))
+        if self._paged:
+            # one graph for every horizon: the kernel takes lengths and
+            # block tables from device memory, and its grid is static
+            graph, logits = self._ensure_graph("paged")
+        else:
+            need = max(self._host_lens[s] for s in active) + 1
+            graph, logits = self._ensure_graph(self._bucket_for(need))
         toks = [0] * self.max_batch
         act = [0] * self.max_batch
         for s in active:
@@ -278,6 +384,17 @@ class BatchedGenerator:
 
     # -- eager path (CPU, or KT_DECODE_GRAPH=0) ------------------------------
     def _decode_eager(self, active):
+        if self._paged:
+            idx = torch.tensor(active, device=self.device)
+            toks = torch.tensor([self.slots[s].next_tok for s in active],
+                                device=self.device)
+            logits = self._paged_math(toks, self.lens[idx],
+                                      torch.ones_like(idx),
+                                      self._pkv.block_table[idx])
+            self.lens[idx] += 1
+            for j, s in enumerate(active):
+                self._emit(self.slots[s], logits[j])
+            return
         cfg = self.cfg
         m = self.model
         idx = torch.tensor(active, device=self.device)

@@ -407,6 +407,151 @@ def flash_attention_v3_supported(S, head_dim, device, dtype):
 
 
 # ---------------------------------------------------------------------------
+# Paged KV cache (serving decode): page write + single-token attention.
+# Inference-only, no autograd. Pools are [num_pages, n_kv, page_size, hd].
+# ---------------------------------------------------------------------------
+PAGED_PAGE_SIZES = (16, 32, 64)
+PAGED_HEAD_DIMS = (64, 128)
+PAGED_GROUPS = (1, 2, 4, 8)
+
+
+def _no_grad_inputs(name, *tensors):
+    if any(t.requires_grad for t in tensors):
+        raise RuntimeError(f"{name} is inference-only: an input requires grad")
+
+
+def _check_pools(k_pages, v_pages):
+    if k_pages.dim() != 4 or v_pages.shape != k_pages.shape:
+        raise ValueError("k_pages/v_pages must be equal-shaped "
+                         "[num_pages, n_kv, page_size, hd]")
+    if not (k_pages.is_contiguous() and v_pages.is_contiguous()):
+        raise ValueError("k_pages/v_pages must be contiguous")
+    if k_pages.shape[2] not in PAGED_PAGE_SIZES:
+        raise ValueError(f"page_size must be one of {PAGED_PAGE_SIZES}")
+    if k_pages.shape[3] not in PAGED_HEAD_DIMS:
+        raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS}")
+
+
+def paged_kv_write(k_new, v_new, k_pages, v_pages, slot_mapping):
+    """Scatter k_new/v_new [T, n_kv, hd] into the page pools in place.
+
+    slot_mapping [T] int32 holds each token's flat physical index
+    page*page_size + offset; a negative entry writes nothing. The result is
+    bitwise what a torch indexed copy gives."""
+    _no_grad_inputs("paged_kv_write", k_new, v_new, k_pages, v_pages)
+    if k_pages.is_cuda:
+        _ext().paged_kv_write(k_new, v_new, k_pages, v_pages, slot_mapping)
+        return
+    _check_pools(k_pages, v_pages)
+    P, Hkv, ps, hd = k_pages.shape
+    if (k_new.shape != v_new.shape or k_new.dim() != 3
+            or tuple(k_new.shape[1:]) != (Hkv, hd)):
+        raise ValueError("k_new/v_new must be [T, n_kv, hd] matching the pool")
+    if slot_mapping.dtype != torch.int32 or \
+            tuple(slot_mapping.shape) != (k_new.shape[0],):
+        raise ValueError("slot_mapping must be [T] int32")
+    slots = slot_mapping.long()
+    keep = (slots >= 0) & (slots < P * ps)
+    page, off = slots[keep] // ps, slots[keep] % ps
+    k_pages[page, :, off] = k_new[keep].to(k_pages.dtype)
+    v_pages[page, :, off] = v_new[keep].to(v_pages.dtype)
+
+
+# Workgroup target of the split heuristic: two workgroups for each of the
+# MI355X's 256 CUs. A workgroup's loop loads a chunk, then computes on it,
+# so a second resident workgroup is what keeps loads in flight meanwhile.
+# Measured at the 8B shape (Hq 32, Hkv 8, hd 128, page 16; kernel + merge,
+# profiles/paged_decode.json "split_sweep"): batch 8 x 4,160 tokens is
+# fastest at 8-12 splits (512-768 workgroups, 39-40 us against 48 us at 4
+# and 47 us at 16), batch 32 x 2,048 at 2-8 splits (65-67 us against 83 us
+# at 1), batch 1 x 8,192 still gains up to 32 splits.
+# _PAGED_MIN_TOKENS_PER_SPLIT keeps a split at four 64-token chunks of the
+# kernel's main loop (16 pages of 16): in the same sweep 260 tokens per
+# split (16 splits of 4,160) is already slower than 347, and at 200 tokens
+# a second split does not pay at batch 32.
+_PAGED_TARGET_WORKGROUPS = 512
+_PAGED_MIN_TOKENS_PER_SPLIT = 256
+_PAGED_MAX_SPLITS = 32
+
+
+def paged_num_splits(batch, n_kv, max_tokens):
+    """Split-KV factor for paged_attention_decode(num_splits=0): enough
+    workgroups to cover the CUs at small batch*n_kv, capped so one split
+    keeps a few pages of the longest possible sequence."""
+    want = -(-_PAGED_TARGET_WORKGROUPS // max(1, batch * n_kv))
+    cap = max(1, max_tokens // _PAGED_MIN_TOKENS_PER_SPLIT)
+    return max(1, min(want, cap, _PAGED_MAX_SPLITS))
+
+
+def _paged_attention_ref(q, k_pages, v_pages, block_table, seq_lens, scale):
+    """fp32 reference: per sequence, gather the valid tokens through the
+    block table and run softmax(q k^T scale) v. Pages that are not
+    referenced and positions >= seq_len are never indexed."""
+    B, Hq, hd = q.shape
+    P, Hkv, ps, _ = k_pages.shape
+    g = Hq // Hkv
+    max_tokens = block_table.shape[1] * ps
+    out = torch.zeros(B, Hq, hd, dtype=torch.float32, device=q.device)
+    lens = seq_lens.tolist()
+    table = block_table.tolist()
+    for b in range(B):
+        n = max(0, min(int(lens[b]), max_tokens))
+        toks = [(table[b][t // ps], t % ps) for t in range(n)]
+        toks = [(p, o) for p, o in toks if 0 <= p < P]
+        if not toks:
+            continue
+        page = torch.tensor([p for p, _ in toks], device=q.device)
+        off = torch.tensor([o for _, o in toks], device=q.device)
+        k = k_pages[page, :, off].float().transpose(0, 1)   # [Hkv, n, hd]
+        v = v_pages[page, :, off].float().transpose(0, 1)
+        qb = q[b].float().view(Hkv, g, hd)
+        p = torch.softmax(torch.matmul(qb, k.transpose(1, 2)) * scale, dim=-1)
+        out[b] = torch.matmul(p, v).view(Hq, hd)
+    return out.to(q.dtype)
+
+
+def paged_attention_decode(q, k_pages, v_pages, block_table, seq_lens,
+                           scale=None, num_splits=0):
+    """Single-token GQA attention over a block-table paged KV cache.
+
+    q [B, Hq, hd]; block_table [B, max_blocks] int32 (-1 = unused);
+    seq_lens [B] int32 = valid tokens per row including the one just
+    written; a row with seq_lens 0 gives zeros. Reads are proportional to
+    each row's own length. num_splits=0 picks a split-KV factor from the
+    table's capacity (paged_num_splits); any fixed value gives the same
+    result up to fp32 merge rounding."""
+    _no_grad_inputs("paged_attention_decode", q, k_pages, v_pages)
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    if num_splits == 0 and k_pages.dim() == 4 and block_table.dim() == 2 \
+            and q.dim() == 3:
+        num_splits = paged_num_splits(
+            q.shape[0], k_pages.shape[1],
+            block_table.shape[1] * k_pages.shape[2])
+    if q.is_cuda:
+        return _ext().paged_attention_decode(q, k_pages, v_pages, block_table,
+                                             seq_lens, float(scale),
+                                             int(num_splits))
+    _check_pools(k_pages, v_pages)
+    if q.dim() != 3 or q.shape[2] != k_pages.shape[3]:
+        raise ValueError("q must be [B, Hq, hd] with the pool's head_dim")
+    Hq, Hkv = q.shape[1], k_pages.shape[1]
+    if Hq % Hkv or Hq // Hkv not in PAGED_GROUPS:
+        raise ValueError(f"group Hq/Hkv must be one of {PAGED_GROUPS}")
+    if q.dtype != k_pages.dtype or q.dtype != v_pages.dtype:
+        raise ValueError("q and the pools must share a dtype")
+    if block_table.dtype != torch.int32 or seq_lens.dtype != torch.int32 \
+            or block_table.dim() != 2 or block_table.shape[0] != q.shape[0] \
+            or tuple(seq_lens.shape) != (q.shape[0],):
+        raise ValueError("block_table [B, max_blocks] and seq_lens [B] "
+                         "must be int32")
+    if num_splits < 1:
+        raise ValueError("num_splits must be >= 0")
+    return _paged_attention_ref(q, k_pages, v_pages, block_table, seq_lens,
+                                float(scale))
+
+
+# ---------------------------------------------------------------------------
 # Multi-tensor pack/unpack (GPU data plane: packed state-dict transfers)
 # ---------------------------------------------------------------------------
 PACK_ALIGN = 16  # bytes; segment starts in the flat buffer are 16B-aligned

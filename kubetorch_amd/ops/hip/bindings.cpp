@@ -54,6 +54,18 @@ void kt_attn_bwd_ck(const void* q, const void* k, const void* v,
                     void* dq_acc, void* dq, void* dk, void* dv, int B, int Hq,
                     int Hkv, int S, float scale, int mask_mode, int pipe,
                     hipStream_t stream);
+void kt_paged_kv_write(const void* k_new, const void* v_new, void* k_pages,
+                       void* v_pages, const void* slot_mapping, long T,
+                       int Hkv, int hd, int page_size, long num_pages,
+                       long k_st, long k_sh, long v_st, long v_sh,
+                       hipStream_t stream);
+int kt_paged_attention_decode(const void* q, const void* k_pages,
+                              const void* v_pages, const void* block_table,
+                              const void* seq_lens, void* out, void* po,
+                              void* pm, void* pl, int B, int Hq, int Hkv,
+                              int hd, int page_size, int num_pages,
+                              int max_blocks, int num_splits, float scale,
+                              hipStream_t stream);
 }
 
 namespace {
@@ -401,6 +413,122 @@ void pack_segments(const at::Tensor& base, const at::Tensor& ptrs,
                    cur_stream(base));
 }
 
+// Shared checks of a paged KV pool pair [num_pages, n_kv, page_size, hd].
+void check_page_pools(const at::Tensor& k_pages, const at::Tensor& v_pages) {
+  CHECK_BF16_CONTIG(k_pages);
+  CHECK_BF16_CONTIG(v_pages);
+  TORCH_CHECK(k_pages.dim() == 4, "k_pages must be [pages, n_kv, page, hd]");
+  TORCH_CHECK(v_pages.sizes() == k_pages.sizes(), "k/v pool shape mismatch");
+  TORCH_CHECK(v_pages.device() == k_pages.device(), "k/v pool device");
+  const int64_t ps = k_pages.size(2), hd = k_pages.size(3);
+  TORCH_CHECK(ps == 16 || ps == 32 || ps == 64,
+              "page_size must be 16, 32 or 64, got ", ps);
+  TORCH_CHECK(hd == 64 || hd == 128, "head_dim must be 64 or 128, got ", hd);
+  TORCH_CHECK(k_pages.size(0) * ps < (int64_t)INT32_MAX,
+              "num_pages*page_size must fit int32");
+}
+
+void paged_kv_write(const at::Tensor& k_new, const at::Tensor& v_new,
+                    at::Tensor k_pages, at::Tensor v_pages,
+                    const at::Tensor& slot_mapping) {
+  // k_new / v_new: [T, n_kv, hd] bf16, token and head dims may be strided
+  // (qkv-split views, prefill-cache views); slot_mapping: [T] int32 flat
+  // physical token index page*page_size + offset, negative = write nothing.
+  check_page_pools(k_pages, v_pages);
+  const int Hkv = (int)k_pages.size(1), ps = (int)k_pages.size(2);
+  const int hd = (int)k_pages.size(3);
+  for (const at::Tensor* t : {&k_new, &v_new}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16,
+                "k_new/v_new must be bf16 on GPU");
+    TORCH_CHECK(t->device() == k_pages.device(), "k_new/v_new device");
+    TORCH_CHECK(t->dim() == 3 && t->size(1) == Hkv && t->size(2) == hd,
+                "k_new/v_new must be [T, n_kv, hd] matching the pool");
+    TORCH_CHECK(t->size(0) == k_new.size(0), "k_new/v_new length mismatch");
+    if (t->numel() == 0) continue;
+    TORCH_CHECK(t->stride(2) == 1, "head dim must be contiguous");
+    // 16 B vector loads: every row start must be 16 B aligned
+    TORCH_CHECK(t->stride(0) % 8 == 0 && t->stride(1) % 8 == 0 &&
+                    reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "k_new/v_new rows must be 16-byte aligned");
+  }
+  const int64_t T = k_new.size(0);
+  TORCH_CHECK(slot_mapping.is_cuda() && slot_mapping.scalar_type() == at::kInt &&
+                  slot_mapping.is_contiguous() && slot_mapping.dim() == 1 &&
+                  slot_mapping.size(0) == T &&
+                  slot_mapping.device() == k_pages.device(),
+              "slot_mapping must be [T] contiguous int32 on the pool's device");
+  if (T == 0) return;
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(k_pages.device());
+  kt_paged_kv_write(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(),
+                    v_pages.data_ptr(), slot_mapping.data_ptr(), (long)T, Hkv,
+                    hd, ps, (long)k_pages.size(0), k_new.stride(0),
+                    k_new.stride(1), v_new.stride(0), v_new.stride(1),
+                    cur_stream(k_pages));
+}
+
+at::Tensor paged_attention_decode(const at::Tensor& q,
+                                  const at::Tensor& k_pages,
+                                  const at::Tensor& v_pages,
+                                  const at::Tensor& block_table,
+                                  const at::Tensor& seq_lens, double scale,
+                                  int64_t num_splits) {
+  // q: [B, Hq, hd]; block_table: [B, max_blocks] int32 (-1 = unused);
+  // seq_lens: [B] int32 valid tokens per row (0 = inactive, zero output).
+  CHECK_BF16_CONTIG(q);
+  check_page_pools(k_pages, v_pages);
+  const int64_t num_pages = k_pages.size(0);
+  const int Hkv = (int)k_pages.size(1), ps = (int)k_pages.size(2);
+  const int hd = (int)k_pages.size(3);
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == hd,
+              "q must be [B, Hq, hd] with the pool's head_dim");
+  TORCH_CHECK(q.device() == k_pages.device(), "q and pools on one device");
+  const int64_t B = q.size(0), Hq = q.size(1);
+  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  const int64_t G = Hq / Hkv;
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8,
+              "group Hq/Hkv must be 1, 2, 4 or 8, got ", G);
+  TORCH_CHECK(block_table.is_cuda() && block_table.scalar_type() == at::kInt &&
+                  block_table.is_contiguous() && block_table.dim() == 2 &&
+                  block_table.size(0) == B &&
+                  block_table.device() == q.device(),
+              "block_table must be [B, max_blocks] contiguous int32 on q's "
+              "device");
+  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.scalar_type() == at::kInt &&
+                  seq_lens.is_contiguous() && seq_lens.dim() == 1 &&
+                  seq_lens.size(0) == B && seq_lens.device() == q.device(),
+              "seq_lens must be [B] contiguous int32 on q's device");
+  const int64_t max_blocks = block_table.size(1);
+  // the kernel's token counters are int32 and step past the end by up to
+  // one chunk (128 tokens) before the loop test
+  TORCH_CHECK(max_blocks * ps < (int64_t)INT32_MAX - 256,
+              "max_blocks*page_size must fit int32");
+  TORCH_CHECK(num_splits >= 1 && num_splits <= 256,
+              "num_splits must be in [1, 256], got ", num_splits);
+  TORCH_CHECK(B * Hkv * num_splits < (int64_t)INT32_MAX, "grid too large");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  auto out = at::empty_like(q);
+  if (B == 0) return out;
+  at::Tensor po, pm, pl;
+  void *po_p = nullptr, *pm_p = nullptr, *pl_p = nullptr;
+  if (num_splits > 1) {
+    auto f32 = q.options().dtype(at::kFloat);
+    po = at::empty({B, Hq, num_splits, hd}, f32);
+    pm = at::empty({B, Hq, num_splits}, f32);
+    pl = at::empty({B, Hq, num_splits}, f32);
+    po_p = po.data_ptr();
+    pm_p = pm.data_ptr();
+    pl_p = pl.data_ptr();
+  }
+  const int rc = kt_paged_attention_decode(
+      q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(),
+      block_table.data_ptr(), seq_lens.data_ptr(), out.data_ptr(), po_p, pm_p,
+      pl_p, (int)B, (int)Hq, Hkv, hd, ps, (int)num_pages, (int)max_blocks,
+      (int)num_splits, (float)scale, cur_stream(q));
+  TORCH_CHECK(rc == 0, "paged_attention_decode: no kernel for head_dim ", hd,
+              " group ", G);
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -431,4 +559,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "One-kernel multi-tensor pack/unpack vs a flat buffer");
   mod.def("attn_bwd_ck", &attn_bwd_ck,
           "CK-tile GQA-native FMHA backward -> (dq, dk_exp, dv_exp)");
+  mod.def("paged_kv_write", &paged_kv_write,
+          "Scatter [T, n_kv, hd] k/v rows into paged pools by slot_mapping");
+  mod.def("paged_attention_decode", &paged_attention_decode,
+          "Single-token GQA attention over a block-table paged KV cache");
 }

@@ -3,7 +3,8 @@
 The flagship model for bench.py (Llama-3-8B DDP bf16 tokens/sec — the
 BASELINE.json north-star config). Hot memory-bound ops run the gfx950 HIP
 kernels from kubetorch_amd.ops (RMSNorm, RoPE, SwiGLU, fused CE); GEMMs go
-to hipBLASLt via torch.nn.Linear; attention uses torch SDPA (flash) on ROCm.
+to hipBLASLt via ops.Linear (nn.Linear with K-contiguous backward
+operands); attention uses torch SDPA (flash) on ROCm.
 
 Reference parity note: the reference (run-house/kubetorch) ships no model
 code at all — it launches user training scripts. This
@@ -108,8 +109,8 @@ class Attention(nn.Module):
         self.cfg = cfg
         d, hd = cfg.dim, cfg.head_dim
         self.n_heads, self.n_kv = cfg.n_heads, cfg.n_kv_heads
-        self.wqkv = nn.Linear(d, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd, bias=False)
-        self.wo = nn.Linear(cfg.n_heads * hd, d, bias=False)
+        self.wqkv = ops.Linear(d, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd, bias=False)
+        self.wo = ops.Linear(cfg.n_heads * hd, d, bias=False)
 
     def _sdpa(self, q, k, v, causal):
         if self.n_kv != self.n_heads:
@@ -203,8 +204,8 @@ class Attention(nn.Module):
 class MLP(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
-        self.w_gate_up = nn.Linear(cfg.dim, 2 * cfg.intermediate, bias=False)
-        self.w_down = nn.Linear(cfg.intermediate, cfg.dim, bias=False)
+        self.w_gate_up = ops.Linear(cfg.dim, 2 * cfg.intermediate, bias=False)
+        self.w_down = ops.Linear(cfg.intermediate, cfg.dim, bias=False)
 
     def forward(self, x):
         return self.w_down(ops.swiglu(self.w_gate_up(x)))
@@ -231,7 +232,7 @@ class Llama(nn.Module):
         self.embed = nn.Embedding(cfg.vocab_size, cfg.dim)
         self.layers = nn.ModuleList(Block(cfg) for _ in range(cfg.n_layers))
         self.norm = RMSNorm(cfg.dim, cfg.norm_eps)
-        self.lm_head = nn.Linear(cfg.dim, cfg.vocab_size, bias=False)
+        self.lm_head = ops.Linear(cfg.dim, cfg.vocab_size, bias=False)
         cos, sin = ops.precompute_rope(cfg.max_seq_len, cfg.head_dim, cfg.rope_base)
         self.register_buffer("rope_cos", cos, persistent=False)
         self.register_buffer("rope_sin", sin, persistent=False)

@@ -628,6 +628,202 @@ def unpack_tensors(flat, tensors, offsets=None):
 
 
 # ---------------------------------------------------------------------------
+# bf16 transposes + bias-free linear with K-contiguous backward operands
+# ---------------------------------------------------------------------------
+def kcontig_enabled():
+    """KT_KCONTIG=0 turns the K-contiguous backward off everywhere (engine
+    shadows and the wgrad layout table), so one tree can run an A/B."""
+    return os.environ.get("KT_KCONTIG", "1") != "0"
+
+
+def _transpose_kernel_ok(src):
+    return (src.is_cuda and src.dtype == torch.bfloat16 and src.dim() == 2
+            and src.shape[0] > 0 and src.shape[1] > 0
+            and src.shape[0] % 8 == 0 and src.shape[1] % 8 == 0
+            and src.stride(1) == 1 and src.stride(0) >= src.shape[1]
+            and src.stride(0) % 8 == 0 and src.data_ptr() % 16 == 0)
+
+
+def transpose_bf16(src):
+    """dst[C, R] = src[R, C].t(), contiguous. bf16 GPU matrices whose dims
+    (and row stride) are multiples of 8 run the LDS-tiled HIP kernel;
+    anything else, and CPU, is .t().contiguous()."""
+    if _transpose_kernel_ok(src):
+        return _ext().transpose_bf16(src)
+    return src.t().contiguous()
+
+
+def transpose_table(segments, src_numel, dst_numel, device):
+    """Device-side segment table for transpose_segments_bf16, built once.
+
+    segments: (src_offset, dst_offset, rows, cols) in elements. Every
+    segment is checked on the host against both buffers (the kernel trusts
+    the table). Returns (table int64 [nseg, 4], max_tiles)."""
+    max_tiles = 0
+    spans = []
+    for so, do, r, c in segments:
+        if min(so, do) < 0 or r <= 0 or c <= 0 or r % 8 or c % 8 \
+                or so % 8 or do % 8:
+            raise ValueError(f"segment {(so, do, r, c)}: offsets, rows and "
+                             "cols must be multiples of 8")
+        if so + r * c > src_numel or do + r * c > dst_numel:
+            raise ValueError(f"segment {(so, do, r, c)} is out of bounds")
+        spans.append((do, do + r * c))
+        max_tiles = max(max_tiles, -(-r // 64) * -(-c // 64))
+    spans.sort()
+    for (_, e0), (s1, _) in zip(spans, spans[1:]):
+        if s1 < e0:
+            raise ValueError("destination segments overlap")
+    table = torch.tensor([list(s) for s in segments], dtype=torch.int64)
+    return table.reshape(-1, 4).to(device), max_tiles
+
+
+def transpose_segments_bf16(flat_src, flat_dst, table, max_tiles):
+    """flat_dst[do : do + r*c] = flat_src[so : so + r*c].view(r, c).t() for
+    every row of `table` (see transpose_table), in one launch on GPU."""
+    if flat_src.is_cuda:
+        _ext().transpose_segments_bf16(flat_src, flat_dst, table, max_tiles)
+        return
+    for so, do, r, c in table.tolist():
+        flat_dst[do:do + r * c].view(c, r).copy_(
+            flat_src[so:so + r * c].view(r, c).t())
+
+
+class ShadowClock:
+    """Write counter of the storage a weight lives in (one per optimizer
+    bucket). Whoever writes the weights outside autograd's view bumps it
+    BEFORE the write; a shadow is fresh only while its stamp matches."""
+    __slots__ = ("value",)
+
+    def __init__(self):
+        self.value = (0, 0)  # (engine step count, other-writer counter)
+
+
+def stamp_weight_t(weight_t, weight, clock=None):
+    """Mark weight_t as holding weight.t() as of now."""
+    weight_t._kt_stamp = (weight._version, clock,
+                          clock.value if clock is not None else None)
+    return weight_t
+
+
+def make_weight_t(weight, clock=None):
+    """A stamped [in, out] shadow of a [out, in] weight."""
+    with torch.no_grad():
+        wt = transpose_bf16(weight.detach())
+    return stamp_weight_t(wt, weight, clock)
+
+
+def weight_t_is_fresh(weight_t, weight):
+    """True only when weight_t was stamped against this weight's current
+    version and its bucket has not been written since. An unstamped or
+    mismatched shadow is never used."""
+    stamp = getattr(weight_t, "_kt_stamp", None)
+    if stamp is None or weight_t.shape != (weight.shape[1], weight.shape[0]):
+        return False
+    version, clock, value = stamp
+    if version != weight._version:
+        return False
+    return clock is None or clock.value == value
+
+
+# wgrad operand layouts for dW[out, in] = dY[T, out]^T @ X[T, in]:
+#   "a"  dY.t() @ X             neither operand K(=T)-contiguous
+#   "b"  dY.t() @ (X^T).t()     X^T materialised by transpose_bf16
+#   "c"  (dY^T) @ X             dY^T materialised
+#   "d"  (dY^T) @ (X^T).t()     both
+# Keyed by (in, out); a layer class is listed only where its GEMM plus
+# transpose time beat "a" in tests/bench_gemm_layouts.py on MI355X
+# (profiles/kcontig_backward.md). Everything else keeps "a".
+WGRAD_VARIANTS = ("a", "b", "c", "d")
+WGRAD_LAYOUT = {
+    (4096, 4096): "b",     # wo:        0.47 -> 0.44 ms at T=16384
+    (4096, 28672): "b",    # w_gate_up: 3.21 -> 2.82 ms
+    (14336, 4096): "c",    # w_down:    1.94 -> 1.81 ms
+    (4096, 128256): "b",   # lm_head:  14.74 -> 12.92 ms
+}
+
+
+def _wgrad(dy2, x2, variant):
+    if variant == "b":
+        return dy2.t() @ transpose_bf16(x2).t()
+    if variant == "c":
+        return transpose_bf16(dy2) @ x2
+    if variant == "d":
+        return transpose_bf16(dy2) @ transpose_bf16(x2).t()
+    return dy2.t() @ x2
+
+
+class _LinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, weight_t, wgrad):
+        ctx.save_for_backward(x, weight)
+        # not a saved tensor: the engine refreshes the shadow in place
+        # between steps, and freshness is judged by its stamp in backward
+        ctx.weight_t = weight_t
+        ctx.wgrad = wgrad
+        return torch.nn.functional.linear(x, weight)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        out_f, in_f = weight.shape
+        dy2 = dy.reshape(-1, out_f)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            wt = ctx.weight_t
+            if wt is not None and weight_t_is_fresh(wt, weight):
+                dx = dy2 @ wt.t()      # both operands K(=out)-contiguous
+            else:
+                dx = dy2 @ weight
+            dx = dx.view(x.shape)
+        if ctx.needs_input_grad[1]:
+            variant = ctx.wgrad
+            if variant is None:
+                variant = (WGRAD_LAYOUT.get((in_f, out_f), "a")
+                           if kcontig_enabled() and dy2.is_cuda else "a")
+            dw = _wgrad(dy2, x.reshape(-1, in_f), variant)
+        return dx, dw, None, None
+
+
+def linear(x, weight, weight_t=None, wgrad=None):
+    """Bias-free y = x @ weight.t() whose backward feeds hipBLASLt
+    K-contiguous operands where that is faster.
+
+    weight_t: optional stamped [in, out] shadow of weight (make_weight_t /
+    stamp_weight_t). dX = dY @ weight_t.t() when it is fresh, else
+    dY @ weight. wgrad: force one of WGRAD_VARIANTS (None = WGRAD_LAYOUT).
+    Without grad this is plain F.linear."""
+    if wgrad is not None and wgrad not in WGRAD_VARIANTS:
+        raise ValueError(f"wgrad must be one of {WGRAD_VARIANTS}")
+    if not torch.is_grad_enabled() or not (x.requires_grad
+                                           or weight.requires_grad):
+        return torch.nn.functional.linear(x, weight)
+    return _LinearFn.apply(x, weight, weight_t, wgrad)
+
+
+class Linear(torch.nn.Linear):
+    """nn.Linear (bias=False only) routed through ops.linear. Parameter and
+    state-dict names are nn.Linear's. weight_t is a plain attribute (not a
+    parameter, not a buffer): FlatDDP installs and refreshes it."""
+
+    def __init__(self, in_features, out_features, bias=False, device=None,
+                 dtype=None):
+        if bias:
+            raise ValueError("ops.Linear is bias-free")
+        super().__init__(in_features, out_features, bias=False, device=device,
+                         dtype=dtype)
+        self.weight_t = None
+
+    def _apply(self, fn, recurse=True):
+        # .to()/.cuda()/.half() give the weight new storage: drop the shadow
+        self.weight_t = None
+        return super()._apply(fn, recurse)
+
+    def forward(self, x):
+        return linear(x, self.weight, self.weight_t)
+
+
+# ---------------------------------------------------------------------------
 # Fused AdamW on flat bf16 buckets (used by kubetorch_amd.parallel)
 # ---------------------------------------------------------------------------
 def adamw_(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):

@@ -49,6 +49,10 @@ void kt_attn_fwd_v3(const void* q, const void* k, const void* v, void* o,
 void kt_pack_segments(const void* ptrs, const void* nbytes, const void* offs,
                       void* base, int nseg, long max_nbytes, int to_base,
                       hipStream_t stream);
+void kt_transpose_bf16(const void* src, long src_stride, void* dst, long R,
+                       long C, hipStream_t stream);
+void kt_transpose_segments_bf16(const void* src, void* dst, const void* table,
+                                int nseg, long max_tiles, hipStream_t stream);
 void kt_attn_bwd_ck(const void* q, const void* k, const void* v,
                     const void* o, const void* do_, const void* lse, void* d,
                     void* dq_acc, void* dq, void* dk, void* dv, int B, int Hq,
@@ -413,6 +417,56 @@ void pack_segments(const at::Tensor& base, const at::Tensor& ptrs,
                    cur_stream(base));
 }
 
+at::Tensor transpose_bf16(const at::Tensor& src) {
+  // dst[C, R] = src[R, C]^T. src rows may be strided (a column slice of a
+  // wider matrix); every 16 B vector the kernel touches must be aligned.
+  TORCH_CHECK(src.is_cuda() && src.scalar_type() == at::kBFloat16,
+              "src must be a bf16 GPU tensor");
+  TORCH_CHECK(src.dim() == 2, "src must be 2-D");
+  const int64_t R = src.size(0), C = src.size(1);
+  TORCH_CHECK(R > 0 && C > 0 && R % 8 == 0 && C % 8 == 0,
+              "rows and cols must be positive multiples of 8");
+  TORCH_CHECK(src.stride(1) == 1 && src.stride(0) >= C &&
+                  src.stride(0) % 8 == 0,
+              "src needs unit column stride and a row stride >= cols that "
+              "is a multiple of 8");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(src.data_ptr()) % 16 == 0,
+              "src must be 16 B aligned");
+  const int64_t tiles = ((R + 63) / 64) * ((C + 63) / 64);
+  TORCH_CHECK(tiles < (int64_t(1) << 31), "too many tiles");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
+  auto dst = at::empty({C, R}, src.options());
+  kt_transpose_bf16(src.data_ptr(), src.stride(0), dst.data_ptr(), R, C,
+                    cur_stream(src));
+  return dst;
+}
+
+void transpose_segments_bf16(const at::Tensor& flat_src, at::Tensor flat_dst,
+                             const at::Tensor& table, int64_t max_tiles) {
+  // table: int64 [nseg, 4] on the device = {src offset, dst offset, rows,
+  // cols} per 2-D segment. The table lives on the device and is not read
+  // back here: ops.transpose_table() validates it against both buffers on
+  // the host when it is built.
+  CHECK_BF16_CONTIG(flat_src);
+  CHECK_BF16_CONTIG(flat_dst);
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == at::kLong &&
+                  table.is_contiguous() && table.dim() == 2 &&
+                  table.size(1) == 4,
+              "table must be a contiguous int64 [nseg, 4] GPU tensor");
+  TORCH_CHECK(flat_src.device() == flat_dst.device() &&
+              flat_src.device() == table.device());
+  const int64_t nseg = table.size(0);
+  TORCH_CHECK(nseg > 0 && nseg < 65536, "1..65535 segments");
+  TORCH_CHECK(max_tiles > 0 && max_tiles < (int64_t(1) << 31));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(flat_src.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(flat_dst.data_ptr()) % 16 == 0,
+              "flat buffers must be 16 B aligned");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(flat_src.device());
+  kt_transpose_segments_bf16(flat_src.data_ptr(), flat_dst.data_ptr(),
+                             table.data_ptr(), (int)nseg, (long)max_tiles,
+                             cur_stream(flat_src));
+}
+
 // Shared checks of a paged KV pool pair [num_pages, n_kv, page_size, hd].
 void check_page_pools(const at::Tensor& k_pages, const at::Tensor& v_pages) {
   CHECK_BF16_CONTIG(k_pages);
@@ -555,6 +609,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("scale_bf16", &scale_bf16,
           "bf16(x * scale), scale one fp32 value in device memory");
   mod.def("adamw_", &adamw_, "Fused AdamW on a flat bf16 bucket");
+  mod.def("transpose_bf16", &transpose_bf16,
+          "dst[C,R] = src[R,C]^T (bf16, LDS-tiled; src rows may be strided)");
+  mod.def("transpose_segments_bf16", &transpose_segments_bf16,
+          "Transpose every 2-D segment of a flat bf16 buffer in one launch");
   mod.def("pack_segments", &pack_segments,
           "One-kernel multi-tensor pack/unpack vs a flat buffer");
   mod.def("attn_bwd_ck", &attn_bwd_ck,

@@ -513,6 +513,107 @@ __global__ void pack_segments_kernel(const unsigned long long* __restrict__ ptrs
 }
 
 // ---------------------------------------------------------------------------
+// bf16 2-D transpose: dst[C, R] = src[R, C]^T (src rows may be strided, dst
+// is contiguous). Feeds the backward GEMMs K-contiguous operands: W^T
+// shadows for dgrad (one launch per optimizer bucket, transpose_segments)
+// and X^T / dY^T for wgrad (transpose_bf16).
+//
+// One 256-thread block moves a 64x64 tile through LDS. Global traffic is
+// 16 B per lane on both sides (R, C and the row stride are multiples of 8;
+// the host checks). The LDS image keeps the source orientation, one dword
+// per bf16 pair, 33 dwords per row (32 + 1 pad):
+//  - fill: lane (row, vec) writes dwords row*33 + vec*4 + k. A 32-lane half
+//    holds rows r..r+3 x vec 0..7 -> banks r + 4*vec + k, all distinct.
+//  - drain: a lane owns source columns (2cp, 2cp+1) x 8 source rows: it
+//    reads 8 dwords down that column pair, splits them into two 8-element
+//    rows of dst and stores 16 B to each. A 32-lane half holds 4 row groups
+//    x 8 column pairs -> banks (8*rg + cp + j) mod 32, all distinct, while
+//    4 lanes x 2 halves still cover one 128 B run of a dst row.
+// Edge tiles: loads and stores past R or C are predicated off (vector
+// granularity is exact because R and C are multiples of 8).
+// ---------------------------------------------------------------------------
+#define TR_TILE 64
+#define TR_PITCH 33
+
+template <bool NT>
+__device__ __forceinline__ void transpose_tile_bf16(
+    const u16* __restrict__ src, long src_stride, u16* __restrict__ dst,
+    long R, long C, long r0, long c0, unsigned int* __restrict__ tile) {
+  const int tid = threadIdx.x;
+  const int lv = tid & 7;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int lr = (tid >> 3) + h * 32;
+    const long r = r0 + lr, c = c0 + lv * 8;
+    if (r < R && c < C) {
+      const vec4ui* gp =
+          reinterpret_cast<const vec4ui*>(src + r * src_stride + c);
+      vec4ui v = NT ? __builtin_nontemporal_load(gp) : *gp;
+      unsigned int* t = tile + lr * TR_PITCH + lv * 4;
+      t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
+    }
+  }
+  __syncthreads();
+  const int lane = tid & 63, l = lane & 31;
+  const int rg = (lane >> 5) * 4 + (l & 3);   // group of 8 source rows
+  const int cp = (tid >> 6) * 8 + (l >> 2);   // source column pair
+  const long c = c0 + 2 * cp, r = r0 + rg * 8;
+  if (c < C && r < R) {
+    unsigned int w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = tile[(rg * 8 + j) * TR_PITCH + cp];
+    vec4ui lo, hi;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      lo[k] = (w[2 * k] & 0xffffu) | (w[2 * k + 1] << 16);
+      hi[k] = (w[2 * k] >> 16) | (w[2 * k + 1] & 0xffff0000u);
+    }
+    vec4ui* d0 = reinterpret_cast<vec4ui*>(dst + c * R + r);
+    vec4ui* d1 = reinterpret_cast<vec4ui*>(dst + (c + 1) * R + r);
+    if (NT) {
+      __builtin_nontemporal_store(lo, d0);
+      __builtin_nontemporal_store(hi, d1);
+    } else {
+      *d0 = lo;
+      *d1 = hi;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256)
+transpose_bf16_kernel(const u16* __restrict__ src, long src_stride,
+                      u16* __restrict__ dst, long R, long C, long tiles_c) {
+  __shared__ unsigned int tile[TR_TILE * TR_PITCH];
+  const long t = blockIdx.x;
+  transpose_tile_bf16<false>(src, src_stride, dst, R, C,
+                             (t / tiles_c) * TR_TILE, (t % tiles_c) * TR_TILE,
+                             tile);
+}
+
+// Every 2-D segment of a flat buffer in one launch. table[seg] = {src
+// offset, dst offset, rows, cols} in elements (offsets multiples of 8);
+// blockIdx.y = segment, x grid-strides over that segment's tiles (blocks
+// past a small segment's tile count exit at once). Streaming: the weights
+// were just written by AdamW and the shadows are read a step later, so
+// both sides bypass L2 retention like adamw_kernel.
+__global__ void __launch_bounds__(256)
+transpose_segments_bf16_kernel(const u16* __restrict__ src,
+                               u16* __restrict__ dst,
+                               const long* __restrict__ table) {
+  __shared__ unsigned int tile[TR_TILE * TR_PITCH];
+  const long* e = table + 4 * (long)blockIdx.y;
+  const long so = e[0], dofs = e[1], R = e[2], C = e[3];
+  const long tiles_c = (C + TR_TILE - 1) / TR_TILE;
+  const long nt = ((R + TR_TILE - 1) / TR_TILE) * tiles_c;
+  for (long t = blockIdx.x; t < nt; t += gridDim.x) {
+    transpose_tile_bf16<true>(src + so, C, dst + dofs, R, C,
+                              (t / tiles_c) * TR_TILE, (t % tiles_c) * TR_TILE,
+                              tile);
+    __syncthreads();  // tile is refilled by the next iteration
+  }
+}
+
+// ---------------------------------------------------------------------------
 // C launchers
 // ---------------------------------------------------------------------------
 static inline int grid_for(long work, int block, int cap = 2048) {
@@ -616,6 +717,23 @@ void kt_pack_segments(const void* ptrs, const void* nbytes, const void* offs,
                      stream, (const unsigned long long*)ptrs,
                      (const long*)nbytes, (const long*)offs, (char*)base,
                      to_base);
+}
+
+void kt_transpose_bf16(const void* src, long src_stride, void* dst, long R,
+                       long C, hipStream_t stream) {
+  const long tiles_c = (C + TR_TILE - 1) / TR_TILE;
+  const long nt = ((R + TR_TILE - 1) / TR_TILE) * tiles_c;
+  hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)nt), dim3(256), 0,
+                     stream, (const u16*)src, src_stride, (u16*)dst, R, C,
+                     tiles_c);
+}
+
+void kt_transpose_segments_bf16(const void* src, void* dst, const void* table,
+                                int nseg, long max_tiles, hipStream_t stream) {
+  int gx = grid_for(max_tiles, 1, 4096);
+  hipLaunchKernelGGL(transpose_segments_bf16_kernel, dim3(gx, nseg), dim3(256),
+                     0, stream, (const u16*)src, (u16*)dst,
+                     (const long*)table);
 }
 
 }  // extern "C"

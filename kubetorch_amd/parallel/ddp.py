@@ -59,7 +59,8 @@ def init_distributed(backend=None, timeout_s=300):
 class _Bucket:
     __slots__ = ("params", "flat_param", "flat_grad", "m", "v", "offsets",
                  "pending", "work", "numel", "completions", "shard_grad",
-                 "ema")
+                 "ema", "flat_param_t", "t_items", "t_table", "t_max_tiles",
+                 "t_fallback", "clock")
 
     def __init__(self):
         self.params: List[torch.nn.Parameter] = []
@@ -72,6 +73,13 @@ class _Bucket:
         self.work = None
         self.numel = 0
         self.completions = 0
+        # K-contiguous dgrad shadows (FlatDDP._build_shadows)
+        self.flat_param_t = None
+        self.t_items = []
+        self.t_table = None
+        self.t_max_tiles = 0
+        self.t_fallback = []
+        self.clock = None
 
 
 def _align8(n):
@@ -89,7 +97,7 @@ class FlatDDP:
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.95), eps=1e-8,
                  weight_decay=0.1, bucket_mb=256, process_group=None,
                  overlap_optimizer=True, grad_accum_steps=1, clip_norm=None,
-                 zero=False, ema_decay=None):
+                 zero=False, ema_decay=None, transposed_shadows=None):
         self.model = model
         self.lr = lr
         self.betas = betas
@@ -206,6 +214,91 @@ class FlatDDP:
                 p.register_post_accumulate_grad_hook(self._grad_ready)
             b.pending = len(b.params)
         self._hooks_enabled = True
+        # W^T shadows for dgrad: on by default on GPU, forced either way by
+        # transposed_shadows (CPU runs take the torch transposes), and off
+        # everywhere under KT_KCONTIG=0.
+        if transposed_shadows is None:
+            transposed_shadows = dev.type == "cuda"
+        self.shadows_enabled = bool(transposed_shadows) and \
+            ops.kcontig_enabled()
+        if self.shadows_enabled:
+            self._build_shadows(dtype, dev)
+            self.refresh_transposed()
+
+    # -- K-contiguous dgrad shadows -----------------------------------------
+    def _build_shadows(self, dtype, dev):
+        """One flat W^T buffer per bucket holding an [in, out] copy of every
+        ops.Linear weight in it (other params get none), installed on the
+        modules as weight_t. The device-side segment table for the one-launch
+        refresh is built here, once."""
+        mods_of = {}
+        for mod in self.model.modules():
+            if isinstance(mod, ops.Linear):
+                mods_of.setdefault(mod.weight, []).append(mod)
+        use_kernel = dev.type == "cuda" and dtype == torch.bfloat16
+        for b in self.buckets:
+            b.clock = ops.ShadowClock()
+            t_numel = 0
+            for p, off in zip(b.params, b.offsets):
+                if p in mods_of and p.dim() == 2:
+                    b.t_items.append((mods_of[p], p, off, t_numel))
+                    t_numel += _align8(p.numel())
+            if not b.t_items:
+                continue
+            b.flat_param_t = torch.zeros(t_numel, dtype=dtype, device=dev)
+            segs = []
+            for item in b.t_items:
+                mods, p, off, toff = item
+                wt = b.flat_param_t[toff:toff + p.numel()].view(
+                    p.shape[1], p.shape[0])
+                for mod in mods:
+                    mod.weight_t = wt
+                if use_kernel and p.shape[0] % 8 == 0 and p.shape[1] % 8 == 0:
+                    segs.append((off, toff, p.shape[0], p.shape[1]))
+                else:
+                    b.t_fallback.append(item)
+            if segs:
+                b.t_table, b.t_max_tiles = ops.transpose_table(
+                    segs, b.flat_param.numel(), t_numel, dev)
+
+    def _touch(self, b):
+        """The bucket's params are about to be written: every shadow stamped
+        before this no longer counts as fresh."""
+        if b.clock is not None:
+            b.clock.value = (self.step_count, b.clock.value[1] + 1)
+
+    def _refresh_bucket(self, b):
+        """Recompute the bucket's shadows from flat_param on the current
+        stream and stamp them fresh."""
+        if b.flat_param_t is None:
+            return
+        if b.t_table is not None:
+            ops.transpose_segments_bf16(b.flat_param, b.flat_param_t,
+                                        b.t_table, b.t_max_tiles)
+        for mods, p, _, _ in b.t_fallback:
+            mods[0].weight_t.copy_(p.detach().t())
+        for mods, p, _, _ in b.t_items:
+            ops.stamp_weight_t(mods[0].weight_t, p, b.clock)
+
+    def mark_params_written(self):
+        """Call before writing flat_param from outside the engine; follow
+        the write with refresh_transposed()."""
+        for b in self.buckets:
+            self._touch(b)
+
+    @torch.no_grad()
+    def refresh_transposed(self):
+        """Rebuild every W^T shadow from the current params. Required after
+        any write to flat_param (or to a param in place) that the engine
+        did not make itself. Between mark_params_written() (or an in-place
+        write through the parameter, which bumps its version) and this
+        call, ops.linear sees a stale stamp and uses the plain dY @ W
+        path; a raw write to flat_param alone is invisible until here."""
+        if not self.shadows_enabled:
+            return
+        for b in self.buckets:
+            self._touch(b)
+            self._refresh_bucket(b)
 
     # -- backward-side -------------------------------------------------------
     def _grad_ready(self, p):
@@ -263,11 +356,16 @@ class FlatDDP:
             if b.work is not None:
                 b.work.wait()  # syncs the side stream with the RCCL stream
                 b.work = None
+            self._touch(b)
             ops.adamw_(
                 b.flat_param, b.flat_grad, b.m, b.v, self.lr,
                 self.betas[0], self.betas[1], self.eps, self.weight_decay,
                 self.step_count, self._grad_scale,
             )
+            # same side stream, right behind the update: hidden under the
+            # rest of backward like AdamW itself; step() joins the stream
+            # before the next forward
+            self._refresh_bucket(b)
 
     # -- optimizer side ------------------------------------------------------
     @torch.no_grad()
@@ -306,11 +404,13 @@ class FlatDDP:
                 if norm > self.clip_norm:
                     grad_scale *= self.clip_norm / (norm + 1e-6)
             for b in self.buckets:
+                self._touch(b)
                 ops.adamw_(
                     b.flat_param, b.flat_grad, b.m, b.v, self.lr,
                     self.betas[0], self.betas[1], self.eps, self.weight_decay,
                     self.step_count, grad_scale,
                 )
+                self._refresh_bucket(b)
         for b in self.buckets:
             if not self._copy_mode:
                 b.flat_grad.zero_()
@@ -369,6 +469,7 @@ class FlatDDP:
         for b in self.buckets:
             sh = b.numel // world
             shard_param = b.flat_param[rank * sh:(rank + 1) * sh]
+            self._touch(b)
             ops.adamw_(
                 shard_param, b.shard_grad, b.m, b.v, self.lr,
                 self.betas[0], self.betas[1], self.eps, self.weight_decay,
@@ -377,6 +478,7 @@ class FlatDDP:
             # all-gather the updated shards in place (chunks are views)
             chunks = list(b.flat_param.chunk(world))
             dist.all_gather(chunks, shard_param, group=self.pg)
+            self._refresh_bucket(b)
 
     def zero_grad(self):
         for b in self.buckets:
@@ -413,9 +515,11 @@ class FlatDDP:
     @torch.no_grad()
     def broadcast_params(self, src=0):
         """Sync initial params across ranks (one collective per bucket)."""
+        self.mark_params_written()
         if self._world > 1:
             for b in self.buckets:
                 dist.broadcast(b.flat_param, src=src, group=self.pg)
+        self.refresh_transposed()
 
     def state_dict(self):
         # NOTE: with zero=True, m/v hold only this rank's shard — resume
@@ -430,7 +534,9 @@ class FlatDDP:
 
     def load_state_dict(self, sd):
         self.step_count = sd["step"]
+        self.mark_params_written()
         for b, m, v, fp in zip(self.buckets, sd["m"], sd["v"], sd["flat_param"]):
             b.m.copy_(m)
             b.v.copy_(v)
             b.flat_param.copy_(fp)
+        self.refresh_transposed()

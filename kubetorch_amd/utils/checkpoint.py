@@ -100,7 +100,10 @@ def load_engine_checkpoint_fast(engine, path):
     for b in engine.buckets:
         tensors += [b.flat_param, b.m, b.v]
     assert len(tensors) == len(manifest["buckets"]), "bucket layout mismatch"
-    return ops._spill_ext().restore_from_file(path, tensors)
+    engine.mark_params_written()
+    ret = ops._spill_ext().restore_from_file(path, tensors)
+    engine.refresh_transposed()
+    return ret
 
 
 def save_engine_checkpoint(model, engine, path, store_key=None):
@@ -127,8 +130,10 @@ def load_engine_checkpoint(model, engine, path_or_key):
     model.load_state_dict(sd["model"])
     eng = sd["engine"]
     engine.step_count = eng["step"]
+    engine.mark_params_written()
     for b, m, v, fp in zip(engine.buckets, eng["m"], eng["v"],
                            eng["flat_param"]):
         b.m.copy_(m)
         b.v.copy_(v)
         b.flat_param.copy_(fp)
+    engine.refresh_transposed()

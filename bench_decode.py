@@ -6,10 +6,18 @@ on one GPU. Usage:
 
     python bench_decode.py --model llama3-8b --batch 8 --prompt 128 --new 128
     python bench_decode.py ... --kv paged [--page-size 16] [--num-splits 0]
+    python bench_decode.py ... --kv paged --prefill paged
+    python bench_decode.py ... --kv paged --prefix-cache --shared-prefix 2048
 
 --kv slot (default) is the padded slot cache; --kv paged the block-table
 page pools with the fused decode-attention kernel. --num-splits 0 lets the
-engine choose the split-KV factor.
+engine choose the split-KV factor. --prefill paged prefills straight into
+the pages with the paged prefill kernel; --prefix-cache shares prompt pages
+between requests. --shared-prefix N makes the first N prompt tokens the
+same for every request and every run; one engine then serves the warm-up
+and the timed runs, so with --prefix-cache the timed run hits the pages the
+warm-up left. ttft_ms is the wall time of the first step() (all prefills
+plus one decode step), device-synchronised.
 """
 import argparse
 import json
@@ -35,32 +43,50 @@ def build_model(name, dev):
     return model, cfg
 
 
-def run_once(model, cfg, batch, prompt, new, kv="slot", page_size=16,
-             num_splits=0):
-    """One full engine run; returns the number of generated tokens."""
+def make_engine(model, batch, prompt, new, kv="slot", page_size=16,
+                num_splits=0, prefill="cache", prefix_cache=False):
     from kubetorch_amd.models import BatchedGenerator
 
     kw = {}
     if kv != "slot":  # the slot run is the constructor's default call
         kw = dict(kv=kv, page_size=page_size, num_splits=num_splits or None)
-    eng = BatchedGenerator(model, max_batch=batch, max_len=prompt + new + 8,
-                           **kw)
+    if prefill != "cache" or prefix_cache:
+        kw.update(prefill=prefill, prefix_cache=prefix_cache)
+    return BatchedGenerator(model, max_batch=batch, max_len=prompt + new + 8,
+                            **kw)
+
+
+def run_once(dev, model, cfg, batch, prompt, new, eng=None, shared=None,
+             **mode):
+    """One full engine run: (generated tokens, seconds of the first step).
+    `shared`: the prompt tokens every request starts with."""
+    if eng is None:
+        eng = make_engine(model, batch, prompt, new, **mode)
+    shared = shared or []
     for i in range(batch):
-        p = torch.randint(0, cfg.vocab_size, (prompt,))
-        eng.submit(p.tolist(), max_new_tokens=new)
-    out = eng.run()
-    return sum(len(v) - prompt for v in out.values())
-
-
-def timed_run(dev, *args, **kw):
-    """(generated tokens, seconds) of one run_once, device-synchronised."""
+        p = torch.randint(0, cfg.vocab_size, (prompt - len(shared),))
+        eng.submit(shared + p.tolist(), max_new_tokens=new)
     if dev.type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    new_toks = run_once(*args, **kw)
+    eng.step()
     if dev.type == "cuda":
         torch.cuda.synchronize()
-    return new_toks, time.perf_counter() - t0
+    ttft = time.perf_counter() - t0
+    out = eng.run()
+    return sum(len(v) - prompt for v in out.values()), ttft
+
+
+def timed_run(dev, *args, **kw):
+    """(generated tokens, seconds, first-step seconds) of one run_once,
+    device-synchronised."""
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    new_toks, ttft = run_once(dev, *args, **kw)
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    return new_toks, time.perf_counter() - t0, ttft
 
 
 def main():
@@ -75,18 +101,45 @@ def main():
     ap.add_argument("--page-size", type=int, default=16)
     ap.add_argument("--num-splits", type=int, default=0,
                     help="paged split-KV factor; 0 = engine's choice")
+    ap.add_argument("--prefill", default="cache", choices=["cache", "paged"],
+                    help="paged: prefill into the pages (needs --kv paged)")
+    ap.add_argument("--prefix-cache", action="store_true",
+                    help="share prompt pages between requests (--kv paged)")
+    ap.add_argument("--shared-prefix", type=int, default=0,
+                    help="first N prompt tokens equal across requests and "
+                         "runs; one engine serves all runs")
     args = ap.parse_args()
+    if not 0 <= args.shared_prefix <= args.prompt:
+        ap.error("--shared-prefix must be in [0, --prompt]")
 
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model, cfg = build_model(args.model, dev)
     run = (model, cfg, args.batch, args.prompt, args.new)
     mode = dict(kv=args.kv, page_size=args.page_size,
                 num_splits=args.num_splits)
+    if args.prefill != "cache" or args.prefix_cache:
+        mode.update(prefill=args.prefill, prefix_cache=args.prefix_cache)
+    extra = {}
+    eng = None
+    if args.shared_prefix:
+        gen = torch.Generator().manual_seed(1)
+        extra["shared"] = torch.randint(
+            0, cfg.vocab_size, (args.shared_prefix,), generator=gen).tolist()
+        eng = extra["eng"] = make_engine(model, args.batch, args.prompt,
+                                         args.new, **mode)
 
     for _ in range(args.warmup):
-        run_once(*run, **mode)
-    new_toks, dt = timed_run(dev, *run, **mode)
+        run_once(dev, *run, **extra, **mode)
+    hit0 = eng.prefix_stats["hit_tokens"] if eng is not None else 0
+    new_toks, dt, ttft = timed_run(dev, *run, **extra, **mode)
 
+    more = {}
+    if args.prefill != "cache" or args.prefix_cache or args.shared_prefix:
+        more = {"prefill": "paged" if args.prefix_cache else args.prefill,
+                "prefix_cache": args.prefix_cache,
+                "shared_prefix": args.shared_prefix}
+        if eng is not None:
+            more["hit_tokens"] = eng.prefix_stats["hit_tokens"] - hit0
     print(json.dumps({
         "metric": "decode_tokens_per_sec",
         "value": round(new_toks / dt, 2),
@@ -97,6 +150,8 @@ def main():
         "model": args.model,
         "device": dev.type,
         "kv": args.kv,
+        "ttft_ms": round(ttft * 1e3, 3),
+        **more,
     }), flush=True)
     print(f"[decode] {new_toks} tokens in {dt:.2f}s", file=sys.stderr)
 

@@ -10,13 +10,39 @@ pages for prompt + max_new_tokens at admission, so a row of the table never
 changes during a request's life, the captured decode step needs no host work
 per token, and a running request cannot run out of pages (no preemption or
 swap).
+
+prefix_cache=True (opt-in) lets requests whose prompts start with the same
+tokens share whole pages. Registered pages hang in a trie whose edge key is
+(parent node, the page's page_size token ids): an exact comparison, so no
+hash collision can hand out another prompt's KV. Only pages fully covered by
+prompt tokens are registered, and they are never written again (prefill
+writes positions >= the cached tokens, decode positions >= the prompt
+length), so no copy-on-write is needed. Pages are reference-counted; a
+holder of a page holds all its ancestors, so ref(parent) >= ref(child) and
+an idle (refcount 0) node's whole subtree is idle. Idle registered pages
+stay cached on an LRU list until the allocator needs them; evicting a node
+drops its whole subtree from the trie, so no unreachable page stays
+registered and a page reused for other content cannot be hit through an
+old path.
 """
+from collections import OrderedDict
+
 import torch
+
+
+class _Node:
+    __slots__ = ("page", "parent", "key", "children")
+
+    def __init__(self, page, parent, key):
+        self.page = page
+        self.parent = parent
+        self.key = key
+        self.children = {}
 
 
 class PagedKVCache:
     def __init__(self, cfg, num_pages, page_size, max_batch, max_blocks,
-                 device, dtype):
+                 device, dtype, prefix_cache=False):
         if num_pages < 1 or max_blocks < 1 or max_batch < 1:
             raise ValueError("num_pages, max_blocks and max_batch must be >= 1")
         self.num_pages = num_pages
@@ -35,10 +61,17 @@ class PagedKVCache:
         self._owned = [[] for _ in range(max_batch)]
         # LIFO free list: a released request's pages are the next handed out
         self._free = list(range(num_pages - 1, -1, -1))
+        self.prefix_cache = bool(prefix_cache)
+        self._ref = [0] * num_pages       # slots listing the page
+        self._root = _Node(-1, None, None)
+        self._node_of = {}                # registered page -> trie node
+        self._idle = OrderedDict()        # registered, refcount 0; LRU first
+        self.evicted_pages = 0
 
     @property
     def free_pages(self):
-        return len(self._free)
+        """Pages an admission can get: free ones plus idle cached ones."""
+        return len(self._free) + len(self._idle)
 
     def pages_of(self, slot):
         return list(self._owned[slot])
@@ -49,6 +82,15 @@ class PagedKVCache:
     def reserve(self, slot, n_tokens):
         """Give `slot` the pages for n_tokens tokens and fill its table row.
         Returns False, changing nothing, when not enough pages are free."""
+        if self.prefix_cache:
+            return self.reserve_prefix(slot, (), n_tokens) is not None
+        need = self._check_reserve(slot, n_tokens)
+        if need > len(self._free):
+            return False
+        self._set_row(slot, [self._free.pop() for _ in range(need)])
+        return True
+
+    def _check_reserve(self, slot, n_tokens):
         if self._owned[slot]:
             raise RuntimeError(f"slot {slot} already holds pages")
         need = self.pages_needed(n_tokens)
@@ -56,19 +98,107 @@ class PagedKVCache:
             raise ValueError(
                 f"{n_tokens} tokens need {need} pages; a row holds 1.."
                 f"{self.max_blocks}")
-        if need > len(self._free):
-            return False
-        pages = [self._free.pop() for _ in range(need)]
+        return need
+
+    def _set_row(self, slot, pages):
         self._owned[slot] = pages
-        self._host_table[slot, :need] = torch.tensor(pages, dtype=torch.int32)
+        self._host_table[slot, :len(pages)] = torch.tensor(
+            pages, dtype=torch.int32)
         self.block_table[slot].copy_(self._host_table[slot])
-        return True
+
+    def _page_key(self, prompt_tokens, i):
+        ps = self.page_size
+        return tuple(prompt_tokens[i * ps:(i + 1) * ps])
+
+    def reserve_prefix(self, slot, prompt_tokens, n_tokens):
+        """reserve() that reuses cached pages for the longest registered
+        prefix of prompt_tokens (a list of ints), at most (S0-1)//page_size
+        pages so that at least one prompt token is computed. Returns the
+        number of cached tokens, or None, changing nothing, when free plus
+        evictable pages do not cover the rest."""
+        if not self.prefix_cache:
+            raise RuntimeError("reserve_prefix needs prefix_cache=True")
+        need = self._check_reserve(slot, n_tokens)
+        node, matched = self._root, []
+        for i in range(min(max(len(prompt_tokens) - 1, 0) // self.page_size,
+                           need)):
+            node = node.children.get(self._page_key(prompt_tokens, i))
+            if node is None:
+                break
+            matched.append(node.page)
+        rest = need - len(matched)
+        idle_hits = sum(1 for p in matched if self._ref[p] == 0)
+        if rest > len(self._free) + len(self._idle) - idle_hits:
+            return None
+        # pin the matched pages before any eviction: a page with a holder is
+        # not on the idle list, so it cannot be evicted for this request
+        for p in matched:
+            if self._ref[p] == 0:
+                del self._idle[p]
+            self._ref[p] += 1
+        pages = list(matched)
+        for _ in range(rest):
+            if not self._free:
+                self._evict_lru()
+            p = self._free.pop()
+            self._ref[p] = 1
+            pages.append(p)
+        self._set_row(slot, pages)
+        return len(matched) * self.page_size
+
+    def _evict_lru(self):
+        """Drop the least recently used idle node and its whole subtree
+        (all idle, by the refcount invariant) from the trie; their pages go
+        back to the free list."""
+        page = next(iter(self._idle))
+        node = self._node_of[page]
+        del node.parent.children[node.key]
+        stack = [node]
+        while stack:
+            n = stack.pop()
+            stack.extend(n.children.values())
+            del self._node_of[n.page]
+            del self._idle[n.page]
+            self._free.append(n.page)
+            self.evicted_pages += 1
+
+    def publish(self, slot, prompt_tokens):
+        """Register the slot's pages that prompt_tokens cover completely,
+        after its prefill. Where a node already exists for a page's content
+        the existing page stays registered and the slot's copy stays
+        private; nothing below it is registered either, since the slot does
+        not hold that node (ref(parent) >= ref(child))."""
+        if not self.prefix_cache:
+            raise RuntimeError("publish needs prefix_cache=True")
+        pages = self._owned[slot]
+        node = self._root
+        for i in range(min(len(prompt_tokens) // self.page_size, len(pages))):
+            key = self._page_key(prompt_tokens, i)
+            child = node.children.get(key)
+            if child is None:
+                child = _Node(pages[i], node, key)
+                node.children[key] = child
+                self._node_of[pages[i]] = child
+            elif child.page != pages[i]:
+                break
+            node = child
 
     def release(self, slot):
         """Return the slot's pages to the pool and reset its row to -1."""
         if not self._owned[slot]:
             raise RuntimeError(f"slot {slot} holds no pages")
-        self._free.extend(reversed(self._owned[slot]))
+        if not self.prefix_cache:
+            self._free.extend(reversed(self._owned[slot]))
+        else:
+            # deepest page first: it becomes the older LRU entry, so a
+            # prefix outlives its extensions
+            for p in reversed(self._owned[slot]):
+                self._ref[p] -= 1
+                if self._ref[p] == 0:
+                    if p in self._node_of:
+                        self._idle[p] = None
+                    else:
+                        self._free.append(p)
         self._owned[slot] = []
         self._host_table[slot].fill_(-1)
         self.block_table[slot].copy_(self._host_table[slot])

@@ -17,6 +17,16 @@ cache (models/paged_kv.py): pages for prompt + max_new_tokens are reserved
 at admission, new k/v are scattered into pages and attention runs the
 paged decode kernel (ops.paged_attention_decode), whose reads follow each
 sequence's own length; one captured graph serves every horizon.
+
+`prefill="paged"` (opt-in, needs kv="paged") runs the prompts admitted in a
+step() as one packed forward straight into the pages
+(ops.paged_attention_prefill): no throwaway KVCache, prompts of any lengths
+share the forward, and prefill_chunk becomes packed rounds inside the same
+step(). `prefix_cache=True` (implies prefill="paged") reuses the pages of
+an earlier request's prompt for a new prompt that starts with the same
+tokens (models/paged_kv.py); only the rest of the prompt is computed.
+Lookup precedes publication, so requests admitted in the same step() do
+not share pages with each other.
 """
 from dataclasses import dataclass, field
 
@@ -34,14 +44,28 @@ class _Request:
     stop_token: int = None
     out: list = field(default_factory=list)
     slot: int = -1
+    cached_tokens: int = 0        # prompt tokens served from shared pages
 
 
 class BatchedGenerator:
     def __init__(self, model, max_batch=8, max_len=None, device=None,
                  prefill_chunk=None, graph=None, kv="slot", page_size=16,
-                 num_pages=None, num_splits=None):
+                 num_pages=None, num_splits=None, prefill="cache",
+                 prefix_cache=False):
         if kv not in ("slot", "paged"):
             raise ValueError(f"kv must be 'slot' or 'paged', got {kv!r}")
+        if prefill not in ("cache", "paged"):
+            raise ValueError(
+                f"prefill must be 'cache' or 'paged', got {prefill!r}")
+        if (prefill == "paged" or prefix_cache) and kv != "paged":
+            raise ValueError(
+                "prefill='paged' and prefix_cache=True need kv='paged'")
+        self._prefix = bool(prefix_cache)
+        self._prefill_paged = prefill == "paged" or self._prefix
+        self.prefix_stats = {"prompt_tokens": 0, "hit_tokens": 0,
+                             "evicted_pages": 0}
+        # rid -> prompt tokens served from the cache, most recent 4096 rids
+        self.cached_tokens = {}
         self.model = model
         cfg = model.cfg
         self.cfg = cfg
@@ -63,7 +87,8 @@ class BatchedGenerator:
             if num_pages is None:
                 num_pages = max_batch * max_blocks
             self._pkv = PagedKVCache(cfg, num_pages, page_size, max_batch,
-                                     max_blocks, self.device, self.dtype)
+                                     max_blocks, self.device, self.dtype,
+                                     prefix_cache=self._prefix)
             # fixed for the engine's life so the decode grid is static
             # (one captured graph serves every horizon)
             self._num_splits = num_splits or ops.paged_num_splits(
@@ -143,14 +168,31 @@ class BatchedGenerator:
                     # FIFO: if the head does not fit, it and everything
                     # behind it wait for pages freed by a later finish
                     head = self.pending[0]
-                    if not self._pkv.reserve(
-                            slot, head.prompt.numel() + head.max_new_tokens):
+                    n = head.prompt.numel() + head.max_new_tokens
+                    if self._prefix:
+                        hit = self._pkv.reserve_prefix(
+                            slot, head.prompt.tolist(), n)
+                        if hit is None:
+                            break
+                        head.cached_tokens = hit
+                        self.cached_tokens[head.rid] = hit
+                        if len(self.cached_tokens) > 4096:
+                            del self.cached_tokens[next(iter(
+                                self.cached_tokens))]
+                        self.prefix_stats["prompt_tokens"] += \
+                            head.prompt.numel()
+                        self.prefix_stats["hit_tokens"] += hit
+                        self.prefix_stats["evicted_pages"] = \
+                            self._pkv.evicted_pages
+                    elif not self._pkv.reserve(slot, n):
                         break
                 req = self.pending.pop(0)
                 req.slot = slot
                 self.slots[slot] = req
                 admitted.append(req)
-        if admitted:
+        if admitted and self._prefill_paged:
+            self._prefill_packed(admitted)
+        elif admitted:
             by_len = {}
             for req in admitted:
                 by_len.setdefault(req.prompt.numel(), []).append(req)
@@ -221,6 +263,87 @@ class BatchedGenerator:
             ops.paged_kv_write(cache.k[i][j, :, :S0].transpose(0, 1),
                                cache.v[i][j, :, :S0].transpose(0, 1),
                                self._pkv.k[i], self._pkv.v[i], slot_map)
+
+    def _prefill_packed(self, reqs):
+        """Prefill every admitted request in packed forwards over the pages:
+        each round takes the next tokens of every unfinished prompt (all of
+        them, or at most prefill_chunk per request), whatever the lengths.
+        Tokens served by the prefix cache are skipped; a request whose
+        prompt is in gets its first token from the round's logits."""
+        ps = self._pkv.page_size
+        pc = self.prefill_chunk
+        done = {r.rid: r.cached_tokens for r in reqs}
+        todo = list(reqs)
+        while todo:
+            toks, pos, slot_map, cu, seq_lens, last = [], [], [], [0], [], []
+            for r in todo:
+                d0, S0 = done[r.rid], r.prompt.numel()
+                n = min(S0 - d0, pc) if pc else S0 - d0
+                pages = self._pkv.pages_of(r.slot)
+                toks.append(r.prompt[d0:d0 + n])
+                pos.extend(range(d0, d0 + n))
+                slot_map.extend(pages[t // ps] * ps + t % ps
+                                for t in range(d0, d0 + n))
+                cu.append(cu[-1] + n)
+                seq_lens.append(d0 + n)
+                last.append(cu[-1] - 1)
+                done[r.rid] = d0 + n
+            dev = self.device
+            i32 = torch.int32
+            logits = self._prefill_math(
+                torch.cat(toks), torch.tensor(pos).to(dev),
+                torch.tensor(slot_map, dtype=i32).to(dev),
+                self._pkv.block_table[torch.tensor(
+                    [r.slot for r in todo]).to(dev)],
+                torch.tensor(cu, dtype=i32).to(dev),
+                torch.tensor(seq_lens, dtype=i32).to(dev),
+                max(b - a for a, b in zip(cu, cu[1:])),
+                torch.tensor(last).to(dev))
+            rest = []
+            for j, r in enumerate(todo):
+                S0 = r.prompt.numel()
+                if done[r.rid] < S0:
+                    rest.append(r)
+                    continue
+                self.lens[r.slot] = S0
+                self._host_lens[r.slot] = S0
+                r.out = r.prompt.tolist()
+                if self._prefix:  # before _emit, which may release the slot
+                    self._pkv.publish(r.slot, r.out)
+                self._emit(r, logits[j])
+            todo = rest
+
+    def _prefill_math(self, toks, pos, slot_map, table, cu, seq_lens, max_q,
+                      last):
+        """One packed prefill forward over the paged cache, in the style of
+        _paged_math: toks/pos/slot_map [T] are the packed tokens, their
+        positions and physical slots; row j of table/seq_lens and cu[j],
+        cu[j+1] describe request j. New k/v go to their pages before
+        attention reads them. Returns logits [len(last), vocab] of the
+        packed tokens `last`."""
+        cfg, m = self.cfg, self.model
+        T = toks.shape[0]
+        hd, Hq, Hkv = cfg.head_dim, cfg.n_heads, cfg.n_kv_heads
+        eps = cfg.norm_eps
+        cos = m.rope_cos[pos]
+        sin = m.rope_sin[pos]
+        h = m.embed(toks.view(1, T))
+        for i, layer in enumerate(m.layers):
+            n1 = ops.rmsnorm(h, layer.attn_norm.weight, eps)
+            qkv = layer.attn.wqkv(n1)
+            q, k, v = qkv.split([Hq * hd, Hkv * hd, Hkv * hd], dim=-1)
+            q = ops.rope(q.view(1, T, Hq, hd), cos, sin)
+            k = ops.rope(k.view(1, T, Hkv, hd), cos, sin)
+            v = v.view(1, T, Hkv, hd)
+            kp, vp = self._pkv.k[i], self._pkv.v[i]
+            ops.paged_kv_write(k[0], v[0], kp, vp, slot_map)
+            o = ops.paged_attention_prefill(q[0], kp, vp, table, cu,
+                                            seq_lens, max_q)
+            h = h + layer.attn.wo(o.reshape(1, T, -1))
+            n2 = ops.rmsnorm(h, layer.mlp_norm.weight, eps)
+            h = h + layer.mlp(n2)
+        hl = ops.rmsnorm(h[:, last].contiguous(), m.norm.weight, eps)
+        return m.lm_head(hl)[0]
 
     def _sample(self, req, logits):
         if req.temperature > 0:

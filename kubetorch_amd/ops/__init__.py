@@ -551,6 +551,105 @@ def paged_attention_decode(q, k_pages, v_pages, block_table, seq_lens,
                                 float(scale))
 
 
+def _paged_prefill_ref(q, k_pages, v_pages, block_table, cu_q_lens, seq_lens,
+                       scale):
+    """fp32 reference of paged_attention_prefill: per row, gather the keys
+    the row's query tokens may attend through the block table and run an
+    offset-causal softmax. Keys behind table entries outside [0, P) are
+    masked, never indexed; a row with more query tokens than seq_lens[b],
+    tokens at a position >= max_blocks*page_size and tokens at an index
+    outside [0, T) stay zero."""
+    T, Hq, hd = q.shape
+    P, Hkv, ps, _ = k_pages.shape
+    g = Hq // Hkv
+    cap = block_table.shape[1] * ps
+    out = torch.zeros(T, Hq, hd, dtype=torch.float32, device=q.device)
+    cu = cu_q_lens.tolist()
+    lens = seq_lens.tolist()
+    table = block_table.tolist()
+    for b in range(len(lens)):
+        qlen = cu[b + 1] - cu[b]
+        ctx = lens[b] - qlen
+        if ctx < 0:
+            continue
+        # (query token, position) pairs that are computed at all
+        toks = [(cu[b] + i, ctx + i) for i in range(max(0, qlen))
+                if ctx + i < cap and 0 <= cu[b] + i < T]
+        if not toks:
+            continue
+        n = max(pos for _, pos in toks) + 1
+        pages = [table[b][t // ps] for t in range(n)]
+        ok = torch.tensor([0 <= p < P for p in pages], device=q.device)
+        page = torch.tensor([p if 0 <= p < P else 0 for p in pages],
+                            device=q.device)
+        off = torch.arange(n, device=q.device) % ps
+        k = k_pages[page, :, off].float().transpose(0, 1)   # [Hkv, n, hd]
+        v = v_pages[page, :, off].float().transpose(0, 1)
+        k = torch.where(ok.view(1, n, 1), k, torch.zeros_like(k))
+        v = torch.where(ok.view(1, n, 1), v, torch.zeros_like(v))
+        ti = torch.tensor([t for t, _ in toks], device=q.device)
+        pos = torch.tensor([p for _, p in toks], device=q.device)
+        qb = q[ti].float().view(len(toks), Hkv, g, hd).permute(1, 0, 2, 3)
+        s = torch.matmul(qb.reshape(Hkv, -1, hd), k.transpose(1, 2)) * scale
+        s = s.view(Hkv, len(toks), g, n)
+        see = ok.view(1, n) & (torch.arange(n, device=q.device).view(1, n)
+                               <= pos.view(-1, 1))          # [toks, n]
+        s = s.masked_fill(~see.view(1, len(toks), 1, n), float("-inf"))
+        p = torch.softmax(s, dim=-1)
+        # a token none of whose keys is readable: zeros, not NaN
+        p = torch.where(see.any(1).view(1, -1, 1, 1), p, torch.zeros_like(p))
+        o = torch.matmul(p.view(Hkv, -1, n), v).view(Hkv, len(toks), g, hd)
+        out[ti] = o.permute(1, 0, 2, 3).reshape(len(toks), Hq, hd)
+    return out.to(q.dtype)
+
+
+def paged_attention_prefill(q, k_pages, v_pages, block_table, cu_q_lens,
+                            seq_lens, max_q_len, scale=None):
+    """Causal GQA attention of a packed, variable-length batch of query
+    tokens over a block-table paged KV cache.
+
+    q [T, Hq, hd] packed rows (may be a strided view of the qkv GEMM
+    output); block_table [B, max_blocks] int32; cu_q_lens [B+1] int32
+    cumulative query counts, row b owns tokens cu[b] .. cu[b+1]-1; seq_lens
+    [B] int32 = the row's valid tokens including this call's query tokens,
+    whose K/V are already in the pages; max_q_len: host int >= every row's
+    query count. Token i of row b sits at position seq_lens[b] - qlen_b + i
+    and attends keys [0, position]. Returns [T, Hq, hd]; a row with
+    qlen_b > seq_lens[b], tokens at a position >= max_blocks*page_size and
+    tokens of no row are zero."""
+    _no_grad_inputs("paged_attention_prefill", q, k_pages, v_pages)
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    if q.is_cuda:
+        return _ext().paged_attention_prefill(q, k_pages, v_pages,
+                                              block_table, cu_q_lens,
+                                              seq_lens, int(max_q_len),
+                                              float(scale))
+    _check_pools(k_pages, v_pages)
+    if q.dim() != 3 or q.shape[2] != k_pages.shape[3]:
+        raise ValueError("q must be [T, Hq, hd] with the pool's head_dim")
+    Hq, Hkv = q.shape[1], k_pages.shape[1]
+    if Hq % Hkv or Hq // Hkv not in PAGED_GROUPS:
+        raise ValueError(f"group Hq/Hkv must be one of {PAGED_GROUPS}")
+    if q.dtype != torch.bfloat16 and q.dtype != torch.float32:
+        raise ValueError("q must be bf16 (fp32 on the CPU reference path)")
+    if q.dtype != k_pages.dtype or q.dtype != v_pages.dtype:
+        raise ValueError("q and the pools must share a dtype")
+    if block_table.dtype != torch.int32 or block_table.dim() != 2:
+        raise ValueError("block_table must be [B, max_blocks] int32")
+    B = block_table.shape[0]
+    if cu_q_lens.dtype != torch.int32 or tuple(cu_q_lens.shape) != (B + 1,):
+        raise ValueError("cu_q_lens must be [B+1] int32")
+    if seq_lens.dtype != torch.int32 or tuple(seq_lens.shape) != (B,):
+        raise ValueError("seq_lens must be [B] int32")
+    if max_q_len < 0:
+        raise ValueError("max_q_len must be >= 0")
+    if not 0 < scale < float("inf"):
+        raise ValueError("scale must be positive and finite")
+    return _paged_prefill_ref(q, k_pages, v_pages, block_table, cu_q_lens,
+                              seq_lens, float(scale))
+
+
 # ---------------------------------------------------------------------------
 # Multi-tensor pack/unpack (GPU data plane: packed state-dict transfers)
 # ---------------------------------------------------------------------------

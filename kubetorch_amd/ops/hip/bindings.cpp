@@ -2,6 +2,7 @@
 // Host-only translation unit; compiled by hipcc against torch-ROCm's
 // native HIP API surface (c10/hip). No CUDA-compat shims.
 
+#include <cmath>
 #include <cstdlib>
 
 #include <torch/extension.h>
@@ -70,6 +71,13 @@ int kt_paged_attention_decode(const void* q, const void* k_pages,
                               int hd, int page_size, int num_pages,
                               int max_blocks, int num_splits, float scale,
                               hipStream_t stream);
+int kt_paged_attention_prefill(const void* q, const void* k_pages,
+                               const void* v_pages, const void* block_table,
+                               const void* cu_q_lens, const void* seq_lens,
+                               void* out, long T, long q_st, long q_sh, int B,
+                               int Hq, int Hkv, int hd, int page_size,
+                               int num_pages, int max_blocks, int max_q_len,
+                               float scale, hipStream_t stream);
 }
 
 namespace {
@@ -583,6 +591,77 @@ at::Tensor paged_attention_decode(const at::Tensor& q,
   return out;
 }
 
+at::Tensor paged_attention_prefill(const at::Tensor& q,
+                                   const at::Tensor& k_pages,
+                                   const at::Tensor& v_pages,
+                                   const at::Tensor& block_table,
+                                   const at::Tensor& cu_q_lens,
+                                   const at::Tensor& seq_lens,
+                                   int64_t max_q_len, double scale) {
+  // q: [T, Hq, hd] packed rows, token and head dims may be strided (a view
+  // of the qkv GEMM output); block_table: [B, max_blocks] int32;
+  // cu_q_lens: [B+1] int32 cumulative query counts; seq_lens: [B] int32
+  // valid tokens per row including this call's query tokens; max_q_len:
+  // host bound on every row's query count (sizes the grid, no device sync).
+  check_page_pools(k_pages, v_pages);
+  const int64_t num_pages = k_pages.size(0);
+  const int Hkv = (int)k_pages.size(1), ps = (int)k_pages.size(2);
+  const int hd = (int)k_pages.size(3);
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16,
+              "q must be bf16 on GPU");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == hd,
+              "q must be [T, Hq, hd] with the pool's head_dim");
+  TORCH_CHECK(q.device() == k_pages.device(), "q and pools on one device");
+  const int64_t T = q.size(0), Hq = q.size(1);
+  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  const int64_t G = Hq / Hkv;
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8,
+              "group Hq/Hkv must be 1, 2, 4 or 8, got ", G);
+  if (q.numel() > 0) {
+    TORCH_CHECK(q.stride(2) == 1, "q head dim must be contiguous");
+    TORCH_CHECK(q.stride(0) % 8 == 0 && q.stride(1) % 8 == 0 &&
+                    q.stride(0) >= 0 && q.stride(1) >= 0 &&
+                    reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+                "q rows must be 16-byte aligned");
+  }
+  TORCH_CHECK(block_table.is_cuda() && block_table.scalar_type() == at::kInt &&
+                  block_table.is_contiguous() && block_table.dim() == 2 &&
+                  block_table.device() == q.device(),
+              "block_table must be [B, max_blocks] contiguous int32 on q's "
+              "device");
+  const int64_t B = block_table.size(0);
+  TORCH_CHECK(cu_q_lens.is_cuda() && cu_q_lens.scalar_type() == at::kInt &&
+                  cu_q_lens.is_contiguous() && cu_q_lens.dim() == 1 &&
+                  cu_q_lens.size(0) == B + 1 &&
+                  cu_q_lens.device() == q.device(),
+              "cu_q_lens must be [B+1] contiguous int32 on q's device");
+  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.scalar_type() == at::kInt &&
+                  seq_lens.is_contiguous() && seq_lens.dim() == 1 &&
+                  seq_lens.size(0) == B && seq_lens.device() == q.device(),
+              "seq_lens must be [B] contiguous int32 on q's device");
+  const int64_t max_blocks = block_table.size(1);
+  TORCH_CHECK(max_blocks * ps < (int64_t)INT32_MAX - 256,
+              "max_blocks*page_size must fit int32");
+  TORCH_CHECK(scale > 0 && std::isfinite(scale),
+              "scale must be positive and finite");
+  TORCH_CHECK(max_q_len >= 0 && max_q_len < (int64_t)INT32_MAX - 256,
+              "max_q_len must be in [0, 2^31)");
+  TORCH_CHECK(B <= 65535 && Hkv <= 65535, "grid too large");
+  TORCH_CHECK(T * Hq * hd < (int64_t(1) << 46), "q too large");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  auto out = at::zeros({T, Hq, hd}, q.options());
+  if (T == 0 || B == 0 || max_q_len == 0) return out;
+  const int rc = kt_paged_attention_prefill(
+      q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(),
+      block_table.data_ptr(), cu_q_lens.data_ptr(), seq_lens.data_ptr(),
+      out.data_ptr(), (long)T, (long)q.stride(0), (long)q.stride(1), (int)B,
+      (int)Hq, Hkv, hd, ps, (int)num_pages, (int)max_blocks, (int)max_q_len,
+      (float)scale, cur_stream(q));
+  TORCH_CHECK(rc == 0, "paged_attention_prefill: no kernel for head_dim ", hd,
+              " group ", G);
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -621,4 +700,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "Scatter [T, n_kv, hd] k/v rows into paged pools by slot_mapping");
   mod.def("paged_attention_decode", &paged_attention_decode,
           "Single-token GQA attention over a block-table paged KV cache");
+  mod.def("paged_attention_prefill", &paged_attention_prefill,
+          "Causal GQA attention of packed query tokens over a paged KV cache");
 }

@@ -92,6 +92,28 @@ class KVCache:
         if self.pos > self.max_len:
             raise RuntimeError("KV cache overflow")
 
+    def attend(self, i, layer, q, k, v):
+        """`attend` of Llama._walk over this cache: append the chunk, then
+        prefill (pos == 0) is causal over the chunk and a decode step
+        (S == 1) attends over the whole cache."""
+        B, S = q.shape[:2]
+        q, k, v = (t.transpose(1, 2) for t in (q, k, v))
+        kf, vf = self.append(i, k, v)
+        P = self.pos
+        if P == 0:
+            o = layer.attn._sdpa(q, kf, vf, causal=True)
+        elif S == 1:
+            o = layer.attn._sdpa(q, kf, vf)
+        else:
+            # chunked prefill: query row i (position pos+i) attends
+            # keys [0, pos+i] — causal with a column offset
+            L = P + S
+            ar = torch.arange(L, device=q.device)
+            mask = (ar.view(1, L) <= (P + torch.arange(
+                S, device=q.device)).view(S, 1)).view(1, 1, S, L)
+            o = layer.attn._sdpa(q, kf, vf, mask=mask)
+        return o.transpose(1, 2).reshape(B, S, -1)
+
 
 class RMSNorm(nn.Module):
     def __init__(self, dim, eps):
@@ -112,31 +134,22 @@ class Attention(nn.Module):
         self.wqkv = ops.Linear(d, (cfg.n_heads + 2 * cfg.n_kv_heads) * hd, bias=False)
         self.wo = ops.Linear(cfg.n_heads * hd, d, bias=False)
 
-    def _sdpa(self, q, k, v, causal):
+    def _sdpa(self, q, k, v, causal=False, mask=None):
+        """SDPA, causal or under a boolean mask (True = attend; ragged
+        decode batches, offset-causal prefill chunks)."""
+        kw = dict(attn_mask=mask, is_causal=causal)
         if self.n_kv != self.n_heads:
             try:
                 return F.scaled_dot_product_attention(
-                    q, k, v, is_causal=causal, enable_gqa=True)
+                    q, k, v, enable_gqa=True, **kw)
             except (TypeError, RuntimeError):
                 rep = self.n_heads // self.n_kv
                 k = k.repeat_interleave(rep, dim=1)
                 v = v.repeat_interleave(rep, dim=1)
-        return F.scaled_dot_product_attention(q, k, v, is_causal=causal)
+        return F.scaled_dot_product_attention(q, k, v, **kw)
 
-    def _sdpa_masked(self, q, k, v, mask):
-        """Boolean-masked SDPA (True = attend) for ragged decode batches
-        (models/serving.py: per-slot cache lengths)."""
-        if self.n_kv != self.n_heads:
-            try:
-                return F.scaled_dot_product_attention(
-                    q, k, v, attn_mask=mask, enable_gqa=True)
-            except (TypeError, RuntimeError):
-                rep = self.n_heads // self.n_kv
-                k = k.repeat_interleave(rep, dim=1)
-                v = v.repeat_interleave(rep, dim=1)
-        return F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
-
-    def forward(self, x, cos, sin, cache=None, layer=0):
+    def forward(self, x, cos, sin):
+        """Training path; inference goes through Llama._walk."""
         import os
 
         B, S, _ = x.shape
@@ -145,29 +158,6 @@ class Attention(nn.Module):
         q, k, v = qkv.split(
             [self.n_heads * hd, self.n_kv * hd, self.n_kv * hd], dim=-1
         )
-        if cache is not None:
-            # Decode path: cos/sin come pre-sliced at the cache position;
-            # prefill (pos==0) is causal over the chunk, decode steps (S==1)
-            # attend over the whole cache.
-            q = ops.rope(q.view(B, S, self.n_heads, hd), cos, sin)
-            k = ops.rope(k.view(B, S, self.n_kv, hd), cos, sin)
-            v = v.view(B, S, self.n_kv, hd)
-            q, k, v = (t.transpose(1, 2) for t in (q, k, v))
-            kf, vf = cache.append(layer, k, v)
-            if cache.pos == 0:
-                o = self._sdpa(q, kf, vf, causal=True)
-            elif S == 1:
-                o = self._sdpa(q, kf, vf, causal=False)
-            else:
-                # chunked prefill: query row i (position pos+i) attends
-                # keys [0, pos+i] — causal with a column offset
-                P = cache.pos
-                L = P + S
-                ar = torch.arange(L, device=x.device)
-                mask = (ar.view(1, L) <= (P + torch.arange(
-                    S, device=x.device)).view(S, 1)).view(1, 1, S, L)
-                o = self._sdpa_masked(q, kf, vf, mask)
-            return self.wo(o.transpose(1, 2).reshape(B, S, -1))
         attn_impl = os.environ.get("KT_ATTN", "ck")
         # The v3 FMHA kernel wants Q pre-scaled by softmax_scale*log2e (its
         # LSE contract, ops/hip/bindings.cpp) — fold that into the RoPE
@@ -312,6 +302,35 @@ class Llama(nn.Module):
         logits = self.forward(tokens)
         return ops.fused_cross_entropy(logits, targets)
 
+    @torch.no_grad()
+    def _walk(self, h, rope, attend):
+        """The inference layer walk, shared by every cached forward (the
+        KVCache below, the serving engine's slot and paged caches): h is
+        [B, S, dim]; `rope(x)` rotates a [B, S, H, hd] view;
+        `attend(i, layer, q, k, v)` gets layer i's rotated q/k and raw v,
+        stores k/v wherever its cache keeps them and returns the attention
+        output as [B, S, Hq*hd]. The final norm and lm_head (`_head`) stay
+        with the caller, which picks the rows it needs."""
+        cfg = self.cfg
+        B, S, _ = h.shape
+        hd, Hq, Hkv = cfg.head_dim, cfg.n_heads, cfg.n_kv_heads
+        eps = cfg.norm_eps
+        for i, layer in enumerate(self.layers):
+            n1 = ops.rmsnorm(h, layer.attn_norm.weight, eps)
+            q, k, v = layer.attn.wqkv(n1).split(
+                [Hq * hd, Hkv * hd, Hkv * hd], dim=-1)
+            q = rope(q.view(B, S, Hq, hd))
+            k = rope(k.view(B, S, Hkv, hd))
+            v = v.view(B, S, Hkv, hd)
+            h = h + layer.attn.wo(attend(i, layer, q, k, v))
+            h = h + layer.mlp(ops.rmsnorm(h, layer.mlp_norm.weight, eps))
+        return h
+
+    def _head(self, h):
+        """Final norm + lm_head on the rows of h the caller selected."""
+        return self.lm_head(ops.rmsnorm(h.contiguous(), self.norm.weight,
+                                        self.cfg.norm_eps))
+
     def _forward_cached(self, tokens, cache):
         """One forward chunk through the KV cache (prefill or decode step);
         returns logits for the LAST position only."""
@@ -319,15 +338,10 @@ class Llama(nn.Module):
         p = cache.pos
         cos = self.rope_cos[p:p + S]
         sin = self.rope_sin[p:p + S]
-        h = self.embed(tokens)
-        eps = self.cfg.norm_eps
-        for i, layer in enumerate(self.layers):
-            h = h + layer.attn(ops.rmsnorm(h, layer.attn_norm.weight, eps),
-                               cos, sin, cache=cache, layer=i)
-            h = h + layer.mlp(ops.rmsnorm(h, layer.mlp_norm.weight, eps))
+        h = self._walk(self.embed(tokens),
+                       lambda x: ops.rope(x, cos, sin), cache.attend)
         cache.advance(S)
-        h = ops.rmsnorm(h[:, -1:].contiguous(), self.norm.weight, eps)
-        return self.lm_head(h)[:, -1]
+        return self._head(h[:, -1:])[:, -1]
 
     @torch.no_grad()
     def generate(self, tokens, max_new_tokens, temperature=0.0, top_k=None,

@@ -76,6 +76,12 @@ class PagedKVCache:
     def pages_of(self, slot):
         return list(self._owned[slot])
 
+    def token_slots(self, slot, start, stop):
+        """Physical token indices (page * page_size + offset) of positions
+        [start, stop) of `slot`: the slot map paged_kv_write takes."""
+        ps, pages = self.page_size, self._owned[slot]
+        return [pages[t // ps] * ps + t % ps for t in range(start, stop)]
+
     def pages_needed(self, n_tokens):
         return -(-n_tokens // self.page_size)
 

@@ -8,9 +8,12 @@ and runs one batched decode step for every active slot per `step()`;
 prefills fill free slots as requests arrive.
 
 Per-slot positions make the stock forward unusable (RoPE offset and the
-causal horizon differ per row), so the decode step is written against the
-same ops the model uses (rmsnorm/swiglu kernels, SDPA with a length mask),
-keeping numerics aligned with `Llama.generate`.
+causal horizon differ per row). Every step here is instead the model's one
+inference layer walk (`Llama._walk`, the loop behind `Llama.generate` too)
+with a RoPE and an attention back-end plugged in. There are three
+back-ends: the slot cache under a length mask (`_slot_math`), paged decode
+(`_paged_math`) and packed paged prefill (`_prefill_math`); the prompt
+forward through a throwaway KVCache is `Llama._forward_cached` itself.
 
 `kv="paged"` (opt-in) replaces the slot slabs with a block-table paged
 cache (models/paged_kv.py): pages for prompt + max_new_tokens are reserved
@@ -197,52 +200,37 @@ class BatchedGenerator:
             for req in admitted:
                 by_len.setdefault(req.prompt.numel(), []).append(req)
             for group in by_len.values():
-                if len(group) > 1 and not self.prefill_chunk:
-                    self._prefill_batch(group)
-                else:
-                    for req in group:
-                        self._prefill(req)
+                # chunked prefill stays one request at a time
+                for g in ([[r] for r in group] if self.prefill_chunk
+                          else [group]):
+                    self._prefill(g)
         active = [s for s in range(self.max_batch) if self.slots[s] is not None]
         if active:
             self._decode(active)
 
-    def _prefill_batch(self, group):
-        """One forward for G same-length prompts (a 1-at-a-time prefill is
-        GEMM-starved: [1, S0] activations; [G, S0] runs the same layer
-        GEMMs at G-fold arithmetic intensity)."""
+    def _prefill(self, group):
+        """Run G same-length prompts through one throwaway KVCache, in
+        prefill_chunk-token pieces if set, then move each row's KV into its
+        request's slot. (A 1-at-a-time prefill is GEMM-starved: [1, S0]
+        activations; [G, S0] runs the same layer GEMMs at G-fold
+        arithmetic intensity.)"""
         from kubetorch_amd.models.llama import KVCache
 
         S0 = group[0].prompt.numel()
-        G = len(group)
-        batch = torch.stack([req.prompt for req in group])
-        cache = KVCache(self.cfg, G, S0, self.device, self.dtype)
-        logits = self.model._forward_cached(batch, cache)
+        batch = (torch.stack([req.prompt for req in group])
+                 if len(group) > 1 else group[0].prompt.view(1, -1))
+        cache = KVCache(self.cfg, len(group), S0, self.device, self.dtype)
+        pc = self.prefill_chunk
+        chunk = pc if pc and pc < S0 else S0
+        for s0 in range(0, S0, chunk):
+            logits = self.model._forward_cached(batch[:, s0:s0 + chunk],
+                                                cache)
         for j, req in enumerate(group):
             self._store_prefill(req, cache, j, S0)
             self.lens[req.slot] = S0
             self._host_lens[req.slot] = S0
             req.out = req.prompt.tolist()
             self._emit(req, logits[j])
-
-    def _prefill(self, req):
-        """Run the prompt through a throwaway per-request cache, then copy
-        the KV rows into this request's slot."""
-        from kubetorch_amd.models.llama import KVCache
-
-        S0 = req.prompt.numel()
-        cache = KVCache(self.cfg, 1, S0, self.device, self.dtype)
-        pc = self.prefill_chunk
-        if pc and pc < S0:
-            for s0 in range(0, S0, pc):
-                logits = self.model._forward_cached(
-                    req.prompt[s0:s0 + pc].view(1, -1), cache)
-        else:
-            logits = self.model._forward_cached(req.prompt.view(1, -1), cache)
-        self._store_prefill(req, cache, 0, S0)
-        self.lens[req.slot] = S0
-        self._host_lens[req.slot] = S0
-        req.out = req.prompt.tolist()
-        self._emit(req, logits[0])
 
     def _store_prefill(self, req, cache, j, S0):
         """Move row j of a prefill cache into the request's slot (slot
@@ -253,11 +241,8 @@ class BatchedGenerator:
                 self.k[i][req.slot, :, :S0] = cache.k[i][j, :, :S0]
                 self.v[i][req.slot, :, :S0] = cache.v[i][j, :, :S0]
             return
-        ps = self._pkv.page_size
-        pages = self._pkv.pages_of(req.slot)
-        slot_map = torch.tensor(
-            [pages[t // ps] * ps + t % ps for t in range(S0)],
-            dtype=torch.int32).to(self.device)
+        slot_map = torch.tensor(self._pkv.token_slots(req.slot, 0, S0),
+                                dtype=torch.int32).to(self.device)
         for i in range(self.cfg.n_layers):
             # [n_kv, S0, hd] -> [S0, n_kv, hd] views, no copy
             ops.paged_kv_write(cache.k[i][j, :, :S0].transpose(0, 1),
@@ -270,7 +255,6 @@ class BatchedGenerator:
         them, or at most prefill_chunk per request), whatever the lengths.
         Tokens served by the prefix cache are skipped; a request whose
         prompt is in gets its first token from the round's logits."""
-        ps = self._pkv.page_size
         pc = self.prefill_chunk
         done = {r.rid: r.cached_tokens for r in reqs}
         todo = list(reqs)
@@ -279,11 +263,9 @@ class BatchedGenerator:
             for r in todo:
                 d0, S0 = done[r.rid], r.prompt.numel()
                 n = min(S0 - d0, pc) if pc else S0 - d0
-                pages = self._pkv.pages_of(r.slot)
                 toks.append(r.prompt[d0:d0 + n])
                 pos.extend(range(d0, d0 + n))
-                slot_map.extend(pages[t // ps] * ps + t % ps
-                                for t in range(d0, d0 + n))
+                slot_map.extend(self._pkv.token_slots(r.slot, d0, d0 + n))
                 cu.append(cu[-1] + n)
                 seq_lens.append(d0 + n)
                 last.append(cu[-1] - 1)
@@ -321,29 +303,21 @@ class BatchedGenerator:
         cu[j+1] describe request j. New k/v go to their pages before
         attention reads them. Returns logits [len(last), vocab] of the
         packed tokens `last`."""
-        cfg, m = self.cfg, self.model
+        m = self.model
         T = toks.shape[0]
-        hd, Hq, Hkv = cfg.head_dim, cfg.n_heads, cfg.n_kv_heads
-        eps = cfg.norm_eps
         cos = m.rope_cos[pos]
         sin = m.rope_sin[pos]
-        h = m.embed(toks.view(1, T))
-        for i, layer in enumerate(m.layers):
-            n1 = ops.rmsnorm(h, layer.attn_norm.weight, eps)
-            qkv = layer.attn.wqkv(n1)
-            q, k, v = qkv.split([Hq * hd, Hkv * hd, Hkv * hd], dim=-1)
-            q = ops.rope(q.view(1, T, Hq, hd), cos, sin)
-            k = ops.rope(k.view(1, T, Hkv, hd), cos, sin)
-            v = v.view(1, T, Hkv, hd)
+
+        def attend(i, layer, q, k, v):
             kp, vp = self._pkv.k[i], self._pkv.v[i]
             ops.paged_kv_write(k[0], v[0], kp, vp, slot_map)
             o = ops.paged_attention_prefill(q[0], kp, vp, table, cu,
                                             seq_lens, max_q)
-            h = h + layer.attn.wo(o.reshape(1, T, -1))
-            n2 = ops.rmsnorm(h, layer.mlp_norm.weight, eps)
-            h = h + layer.mlp(n2)
-        hl = ops.rmsnorm(h[:, last].contiguous(), m.norm.weight, eps)
-        return m.lm_head(hl)[0]
+            return o.reshape(1, T, -1)
+
+        h = m._walk(m.embed(toks.view(1, T)),
+                    lambda x: ops.rope(x, cos, sin), attend)
+        return m._head(h[:, last])[0]
 
     def _sample(self, req, logits):
         if req.temperature > 0:
@@ -370,42 +344,46 @@ class BatchedGenerator:
             return self._decode_graph(active)
         return self._decode_eager(active)
 
-    # -- hipGraph path -------------------------------------------------------
-    def _decode_math(self, L):
-        """One full-batch decode step over horizon L as a pure function of
-        the static buffers (_g_toks, lens, _g_act) — capturable: fixed
-        shapes, no host syncs, no data-dependent control flow. Inactive
-        slots decode garbage (their mask exposes only cache row 0) and are
-        ignored at emit time; their cache rows are overwritten by the next
-        prefill."""
-        cfg, m = self.cfg, self.model
-        B = self.max_batch
-        hd, Hq, Hkv = cfg.head_dim, cfg.n_heads, cfg.n_kv_heads
-        eps = cfg.norm_eps
-        lens = self.lens
-        cos = m.rope_cos[lens].view(B, 1, 1, hd // 2)
-        sin = m.rope_sin[lens].view(B, 1, 1, hd // 2)
+    # -- decode maths (capturable: no host syncs, no data-dependent flow) -----
+    def _decode_walk(self, toks, lens, attend):
+        """One single-token step for B rows at per-row positions `lens`:
+        the model's layer walk with per-row RoPE tables (fp32) and the
+        cache's `attend`; returns logits [B, vocab]."""
+        m = self.model
+        B = toks.shape[0]
+        half = self.cfg.head_dim // 2
+        cos = m.rope_cos[lens].view(B, 1, 1, half)
+        sin = m.rope_sin[lens].view(B, 1, 1, half)
+        h = m._walk(m.embed(toks).view(B, 1, -1),
+                    lambda x: self._rope1(x, cos, sin), attend)
+        return m._head(h)[:, -1]
+
+    def _slot_math(self, toks, lens, L, idx=None):
+        """One decode step over the slot cache, horizon L: new k/v go to
+        each row's own position and SDPA runs under a length mask (row b
+        sees [0, lens[b]]). idx=None is every slot, read as the view
+        [:, :, :L] (the graph path: fixed shapes, no gather of the cache);
+        inactive slots then decode garbage (their mask exposes only cache
+        row 0), are ignored at emit time, and their cache rows are
+        overwritten by the next prefill. With idx, toks/lens belong to
+        those slots and the cache rows are gathered."""
+        B = toks.shape[0]
+        rows = self._g_rows if idx is None else idx
         ar = torch.arange(L, device=self.device)
         mask = (ar.view(1, L) <= lens.view(B, 1)).view(B, 1, 1, L)
-        h = m.embed(self._g_toks).view(B, 1, cfg.dim)
-        for i, layer in enumerate(m.layers):
-            n1 = ops.rmsnorm(h, layer.attn_norm.weight, eps)
-            qkv = layer.attn.wqkv(n1)
-            q, k, v = qkv.split([Hq * hd, Hkv * hd, Hkv * hd], dim=-1)
-            q = self._rope1(q.view(B, 1, Hq, hd), cos, sin)
-            k = self._rope1(k.view(B, 1, Hkv, hd), cos, sin)
-            v = v.view(B, 1, Hkv, hd)
-            self.k[i][self._g_rows, :, lens] = k[:, 0]
-            self.v[i][self._g_rows, :, lens] = v[:, 0]
-            o = layer.attn._sdpa_masked(q.transpose(1, 2),
-                                        self.k[i][:, :, :L],
-                                        self.v[i][:, :, :L], mask)
-            h = h + layer.attn.wo(o.transpose(1, 2).reshape(B, 1, -1))
-            n2 = ops.rmsnorm(h, layer.mlp_norm.weight, eps)
-            h = h + layer.mlp(n2)
-        logits = m.lm_head(ops.rmsnorm(h, m.norm.weight, eps))[:, -1]
-        self.lens.add_(self._g_act)  # active slots advance one position
-        return logits
+
+        def attend(i, layer, q, k, v):
+            # advanced indexing: [rows, :, lens] -> [B, n_kv, hd] rows
+            self.k[i][rows, :, lens] = k[:, 0]
+            self.v[i][rows, :, lens] = v[:, 0]
+            if idx is None:
+                kf, vf = self.k[i][:, :, :L], self.v[i][:, :, :L]
+            else:
+                kf, vf = self.k[i][idx, :, :L], self.v[i][idx, :, :L]
+            o = layer.attn._sdpa(q.transpose(1, 2), kf, vf, mask=mask)
+            return o.transpose(1, 2).reshape(B, 1, -1)
+
+        return self._decode_walk(toks, lens, attend)
 
     def _paged_math(self, toks, lens, act, table):
         """One decode step over the paged cache for the rows given (all
@@ -415,39 +393,34 @@ class BatchedGenerator:
         and tables from device buffers. No mask tensor, no horizon slice,
         no host sync. Rows with act == 0 write nothing (negative slot) and
         attend over nothing (length 0, zero output)."""
-        cfg, m = self.cfg, self.model
         B = toks.shape[0]
-        hd, Hq, Hkv = cfg.head_dim, cfg.n_heads, cfg.n_kv_heads
-        eps = cfg.norm_eps
         ps = self._pkv.page_size
-        cos = m.rope_cos[lens].view(B, 1, 1, hd // 2)
-        sin = m.rope_sin[lens].view(B, 1, 1, hd // 2)
         blk = (lens // ps).clamp(max=self._pkv.max_blocks - 1)
         page = table.gather(1, blk.view(B, 1)).view(B).long()
         live = (act > 0) & (page >= 0)
         slot_map = torch.where(live, page * ps + lens % ps,
                                torch.full_like(page, -1)).to(torch.int32)
         seq_lens = ((lens + 1) * act).to(torch.int32)
-        h = m.embed(toks).view(B, 1, cfg.dim)
-        for i, layer in enumerate(m.layers):
-            n1 = ops.rmsnorm(h, layer.attn_norm.weight, eps)
-            qkv = layer.attn.wqkv(n1)
-            q, k, v = qkv.split([Hq * hd, Hkv * hd, Hkv * hd], dim=-1)
-            q = self._rope1(q.view(B, 1, Hq, hd), cos, sin)
-            k = self._rope1(k.view(B, 1, Hkv, hd), cos, sin)
-            v = v.view(B, 1, Hkv, hd)
+
+        def attend(i, layer, q, k, v):
             kp, vp = self._pkv.k[i], self._pkv.v[i]
             ops.paged_kv_write(k[:, 0], v[:, 0], kp, vp, slot_map)
             o = ops.paged_attention_decode(q[:, 0], kp, vp, table, seq_lens,
                                            num_splits=self._num_splits)
-            h = h + layer.attn.wo(o.reshape(B, 1, -1))
-            n2 = ops.rmsnorm(h, layer.mlp_norm.weight, eps)
-            h = h + layer.mlp(n2)
-        return m.lm_head(ops.rmsnorm(h, m.norm.weight, eps))[:, -1]
+            return o.reshape(B, 1, -1)
 
-    def _decode_math_paged(self):
-        logits = self._paged_math(self._g_toks, self.lens, self._g_act,
-                                  self._pkv.block_table)
+        return self._decode_walk(toks, lens, attend)
+
+    # -- hipGraph path -------------------------------------------------------
+    def _decode_math(self, L=None):
+        """One full-batch decode step as a pure function of the static
+        buffers (_g_toks, lens, _g_act), which is what a graph captures:
+        over horizon L of the slot cache, or over the pages (no L)."""
+        if self._paged:
+            logits = self._paged_math(self._g_toks, self.lens, self._g_act,
+                                      self._pkv.block_table)
+        else:
+            logits = self._slot_math(self._g_toks, self.lens, L)
         self.lens.add_(self._g_act)  # active slots advance one position
         return logits
 
@@ -471,15 +444,14 @@ class BatchedGenerator:
                                       device=self.device)
             self._g_pool = torch.cuda.graph_pool_handle()
         lens_snapshot = self.lens.clone()
-        math = (self._decode_math_paged if self._paged
-                else lambda: self._decode_math(L))
+        horizon = None if self._paged else L
         for _ in range(2):  # warm up allocator/workspaces pre-capture
-            math()
+            self._decode_math(horizon)
         self.lens.copy_(lens_snapshot)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, pool=self._g_pool):
-            logits = math()
+            logits = self._decode_math(horizon)
         self._graphs[L] = (graph, logits)
         return self._graphs[L]
 
@@ -507,53 +479,17 @@ class BatchedGenerator:
 
     # -- eager path (CPU, or KT_DECODE_GRAPH=0) ------------------------------
     def _decode_eager(self, active):
-        if self._paged:
-            idx = torch.tensor(active, device=self.device)
-            toks = torch.tensor([self.slots[s].next_tok for s in active],
-                                device=self.device)
-            logits = self._paged_math(toks, self.lens[idx],
-                                      torch.ones_like(idx),
-                                      self._pkv.block_table[idx])
-            self.lens[idx] += 1
-            for j, s in enumerate(active):
-                self._emit(self.slots[s], logits[j])
-            return
-        cfg = self.cfg
-        m = self.model
         idx = torch.tensor(active, device=self.device)
         toks = torch.tensor([self.slots[s].next_tok for s in active],
                             device=self.device)
         lens = self.lens[idx]                      # position of the new token
-        B = len(active)
-        hd, Hq, Hkv = cfg.head_dim, cfg.n_heads, cfg.n_kv_heads
-        eps = cfg.norm_eps
-        # per-slot RoPE rows (fp32 tables)
-        cos = m.rope_cos[lens].view(B, 1, 1, hd // 2)
-        sin = m.rope_sin[lens].view(B, 1, 1, hd // 2)
-        L = int(lens.max().item()) + 1             # longest horizon this step
-        # attention mask over the padded cache: slot b sees [0, lens[b]]
-        ar = torch.arange(L, device=self.device)
-        mask = (ar.view(1, L) <= lens.view(B, 1)).view(B, 1, 1, L)
-
-        h = m.embed(toks).view(B, 1, cfg.dim)
-        for i, layer in enumerate(m.layers):
-            n1 = ops.rmsnorm(h, layer.attn_norm.weight, eps)
-            qkv = layer.attn.wqkv(n1)
-            q, k, v = qkv.split([Hq * hd, Hkv * hd, Hkv * hd], dim=-1)
-            q = self._rope1(q.view(B, 1, Hq, hd), cos, sin)
-            k = self._rope1(k.view(B, 1, Hkv, hd), cos, sin)
-            v = v.view(B, 1, Hkv, hd)
-            # append to the slot caches at each slot's own position
-            # (advanced indexing: [idx, :, lens] -> [B, n_kv, hd] rows)
-            self.k[i][idx, :, lens] = k[:, 0]
-            self.v[i][idx, :, lens] = v[:, 0]
-            kf = self.k[i][idx, :, :L]
-            vf = self.v[i][idx, :, :L]
-            o = layer.attn._sdpa_masked(q.transpose(1, 2), kf, vf, mask)
-            h = h + layer.attn.wo(o.transpose(1, 2).reshape(B, 1, -1))
-            n2 = ops.rmsnorm(h, layer.mlp_norm.weight, eps)
-            h = h + layer.mlp(n2)
-        logits = m.lm_head(ops.rmsnorm(h, m.norm.weight, eps))[:, -1]
+        if self._paged:
+            logits = self._paged_math(toks, lens, torch.ones_like(idx),
+                                      self._pkv.block_table[idx])
+        else:
+            # longest horizon this step (a host sync)
+            logits = self._slot_math(toks, lens, int(lens.max().item()) + 1,
+                                     idx)
         self.lens[idx] += 1
         for j, s in enumerate(active):
             self._emit(self.slots[s], logits[j])

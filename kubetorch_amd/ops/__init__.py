@@ -318,61 +318,71 @@ _LN2 = 0.6931471805599453
 LOG2E = 1.4426950408889634
 
 
+def _attention_forward(q, k, v, scale, impl):
+    """-> (q, k, v as saved for backward, o, lse, effective scale)."""
+    if impl == "v3":
+        # AITER-schedule CK v3 kernel (fastest fwd, profiles/). Contract:
+        # q arrives PRE-SCALED by scale*log2e (folded into the RoPE
+        # kernel's oscale), so softmax(scale*q0@kT) == softmax(ln2*q@kT)
+        # and the effective scale for fwd LSE and backward is ln2.
+        o, lse = _ext().attn_fwd_v3(q, k, v, scale, prescaled=True)
+        scale = _LN2
+    elif impl == "ck":
+        # CK path is stride-aware: permuted [B,S,H,D] views go in as-is
+        o, lse = _ext().attn_fwd_ck_tr(q, k, v, scale)
+    else:
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        o, lse = _ext().attn_fwd(q, k, v, scale)
+    return q, k, v, o, lse, scale
+
+
+def _attention_backward_expanded(grad_out, q, k, v, o, lse, scale):
+    """Dense backward -> (dq, dk_e, dv_e), all [B, Hq, S, D]: dk_e and dv_e
+    are per query head (expanded head h belongs to kv head h // g) and still
+    have to be summed over each group."""
+    B, Hq, S, D = q.shape
+    g = Hq // k.shape[1]
+    if os.environ.get("KT_ATTN_BWD") == "ck" and S % 128 == 0:
+        # Opt-in: CK-tile GQA-native bwd (no KV expansion; dk/dv come
+        # back Hq-expanded and are group-summed). Numerically validated
+        # on gfx950 (tests/test_ops.py::test_attn_bwd_ck_gqa_native);
+        # measured 4.42 ms vs 2.99 ms for the aten/AITER-asm path at the
+        # Llama-3-8B shape (B4 H32/8 S4096), so aten stays the default
+        # hot path — see profiles/ROUND2.md lever #1.
+        return tuple(_ext().attn_bwd_ck(
+            grad_out.contiguous(), q.contiguous(), k.contiguous(),
+            v.contiguous(), o.contiguous(), lse.contiguous(), scale))
+    if g > 1:  # expand KV for the dense backward, then reduce over groups
+        k_exp = k.repeat_interleave(g, dim=1)
+        v_exp = v.repeat_interleave(g, dim=1)
+    else:
+        k_exp, v_exp = k, v
+    seed = torch.zeros((), dtype=torch.long, device=q.device)
+    offset = torch.zeros((), dtype=torch.long, device=q.device)
+    dq, dk_e, dv_e, _ = \
+        torch.ops.aten._scaled_dot_product_efficient_attention_backward(
+            grad_out, q, k_exp, v_exp, None, o, lse, seed, offset,
+            0.0, [True, True, True, False], True, scale=scale,
+        )
+    return dq, dk_e, dv_e
+
+
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale, impl):
-        if impl == "v3":
-            # AITER-schedule CK v3 kernel (fastest fwd, profiles/). Contract:
-            # q arrives PRE-SCALED by scale*log2e (folded into the RoPE
-            # kernel's oscale), so softmax(scale*q0@kT) == softmax(ln2*q@kT)
-            # and the effective scale for fwd LSE and backward is ln2.
-            o, lse = _ext().attn_fwd_v3(q, k, v, scale, prescaled=True)
-            scale = _LN2
-        elif impl == "ck":
-            # CK path is stride-aware: permuted [B,S,H,D] views go in as-is
-            o, lse = _ext().attn_fwd_ck_tr(q, k, v, scale)
-        else:
-            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-            o, lse = _ext().attn_fwd(q, k, v, scale)
+        q, k, v, o, lse, scale = _attention_forward(q, k, v, scale, impl)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.scale = scale
         return o
 
     @staticmethod
     def backward(ctx, grad_out):
-        import os
-
         q, k, v, o, lse = ctx.saved_tensors
         B, Hq, S, D = q.shape
         Hkv = k.shape[1]
         g = Hq // Hkv
-        if os.environ.get("KT_ATTN_BWD") == "ck" and S % 128 == 0:
-            # Opt-in: CK-tile GQA-native bwd (no KV expansion; dk/dv come
-            # back Hq-expanded and are group-summed). Numerically validated
-            # on gfx950 (tests/test_ops.py::test_attn_bwd_ck_gqa_native);
-            # measured 4.42 ms vs 2.99 ms for the aten/AITER-asm path at the
-            # Llama-3-8B shape (B4 H32/8 S4096), so aten stays the default
-            # hot path — see profiles/ROUND2.md lever #1.
-            dq, dk_e, dv_e = _ext().attn_bwd_ck(
-                grad_out.contiguous(), q.contiguous(), k.contiguous(),
-                v.contiguous(), o.contiguous(), lse.contiguous(), ctx.scale)
-            if g > 1:
-                dk = dk_e.view(B, Hkv, g, S, D).sum(2)
-                dv = dv_e.view(B, Hkv, g, S, D).sum(2)
-            else:
-                dk, dv = dk_e, dv_e
-            return dq, dk, dv, None, None
-        if g > 1:  # expand KV for the dense backward, then reduce over groups
-            k_exp = k.repeat_interleave(g, dim=1)
-            v_exp = v.repeat_interleave(g, dim=1)
-        else:
-            k_exp, v_exp = k, v
-        seed = torch.zeros((), dtype=torch.long, device=q.device)
-        offset = torch.zeros((), dtype=torch.long, device=q.device)
-        dq, dk, dv, _ = torch.ops.aten._scaled_dot_product_efficient_attention_backward(
-            grad_out.contiguous(), q, k_exp, v_exp, None, o, lse, seed, offset,
-            0.0, [True, True, True, False], True, scale=ctx.scale,
-        )
+        dq, dk, dv = _attention_backward_expanded(
+            grad_out.contiguous(), q, k, v, o, lse, ctx.scale)
         if g > 1:
             dk = dk.view(B, Hkv, g, S, D).sum(2)
             dv = dv.view(B, Hkv, g, S, D).sum(2)
@@ -404,6 +414,160 @@ def flash_attention_v3_supported(S, head_dim, device, dtype):
     return (head_dim == 128 and S % 256 == 0 and S >= 256
             and device.type == "cuda" and dtype == torch.bfloat16
             and hip_available())
+
+
+# ---------------------------------------------------------------------------
+# Attention block as one autograd node: qkv split + RoPE + flash attention
+# forward; dense backward + one kernel for GQA sum, RoPE^T and qkv packing
+# ---------------------------------------------------------------------------
+def attn_pack_enabled():
+    """KT_ATTN_PACK=0 restores the separate rope / attention / sum / cat
+    autograd nodes, so one tree can run an A/B."""
+    return os.environ.get("KT_ATTN_PACK", "1") != "0"
+
+
+def _rope_bwd(dy, cos, sin, oscale):
+    # dy: [B, S, Hh, D], any layout (the GPU reshape copies if it must)
+    if dy.is_cuda:
+        B, S, Hh, D = dy.shape
+        return _ext().rope(dy.reshape(B * S, Hh, D), cos, sin, S, -1.0,
+                           oscale).view(dy.shape)
+    return _rope_ref(dy, cos, sin, -1.0, oscale)
+
+
+def _attn_grad_pack_ref(dq, dk_e, dv_e, cos, sin, n_kv, q_oscale):
+    """The composition attn_grad_pack replaces: bf16 group sums, the rope
+    backward on dq and dk, and the cat into qkv column order. It rounds the
+    k part twice (after the sum and after the rotation)."""
+    B, Hq, S, D = dq.shape
+    g = Hq // n_kv
+    if g > 1:
+        dk = dk_e.reshape(B, n_kv, g, S, D).sum(2)
+        dv = dv_e.reshape(B, n_kv, g, S, D).sum(2)
+    else:
+        dk, dv = dk_e, dv_e
+    dq = _rope_bwd(dq.transpose(1, 2), cos, sin, q_oscale)
+    dk = _rope_bwd(dk.transpose(1, 2), cos, sin, 1.0)
+    return torch.cat([dq.reshape(B, S, Hq * D), dk.reshape(B, S, n_kv * D),
+                      dv.transpose(1, 2).reshape(B, S, n_kv * D)], dim=-1)
+
+
+def _attn_grad_pack_kernel_ok(dq, dk_e, dv_e, cos, sin):
+    """The binding's layout checks (it raises where this returns False)."""
+    for t in (dq, dk_e, dv_e):
+        if not (t.is_cuda and t.dtype == torch.bfloat16
+                and t.device == dq.device and t.stride(3) == 1
+                and t.data_ptr() % 16 == 0):
+            return False
+        if any(t.shape[d] != 1 and (t.stride(d) < 0 or t.stride(d) % 8)
+               for d in range(3)):
+            return False
+    for t in (cos, sin):
+        if not (t.is_cuda and t.device == dq.device
+                and t.dtype == torch.float32 and t.is_contiguous()
+                and t.data_ptr() % 16 == 0):
+            return False
+    return dq.shape[3] % 8 == 0
+
+
+def attn_grad_pack(dq, dk_e, dv_e, cos, sin, n_kv, q_oscale=1.0):
+    """dqkv [B, S, (Hq + 2*n_kv)*D] from the dense attention backward's
+    (dq, dk_e, dv_e), each bf16 [B, Hq, S, D] with dk_e/dv_e per query head:
+
+        q part = q_oscale * R^T(dq)
+        k part = R^T(sum_j dk_e[kv*g + j])      g = Hq // n_kv
+        v part = sum_j dv_e[kv*g + j]
+
+    R^T is the rope backward at position s with the fp32 [>=S, D/2] cos/sin
+    tables. On the GPU one kernel does it in fp32 with a single bf16 round
+    per element; [B,H,S,D] buffers and transposed [B,S,H,D] buffers both go
+    in without a copy. On CPU, and for layouts the kernel does not take, the
+    separate sum / rope / cat composition runs instead."""
+    if dq.dim() != 4 or dk_e.shape != dq.shape or dv_e.shape != dq.shape:
+        raise ValueError("dq, dk_e and dv_e must be equal-shaped "
+                         "[B, Hq, S, D]")
+    B, Hq, S, D = dq.shape
+    if n_kv < 1 or Hq % n_kv:
+        raise ValueError(f"Hq={Hq} is not a multiple of n_kv={n_kv}")
+    if D % 2 or cos.dim() != 2 or cos.shape != sin.shape \
+            or cos.shape[0] < S or cos.shape[1] != D // 2:
+        raise ValueError("cos/sin must be [>=S, D/2] tables")
+    if _attn_grad_pack_kernel_ok(dq, dk_e, dv_e, cos, sin):
+        return _ext().attn_grad_pack(dq, dk_e, dv_e, cos, sin, n_kv,
+                                     q_oscale)
+    return _attn_grad_pack_ref(dq, dk_e, dv_e, cos[:S], sin[:S], n_kv,
+                               q_oscale)
+
+
+def _qkv_split_rope(qkv, cos, sin, n_heads, n_kv, impl):
+    """-> rotated q [B,Hq,S,D], rotated k and raw v [B,Hkv,S,D] as views of
+    [B,S,H,D] buffers, and the scale folded into q (v3: scale*log2e)."""
+    B, S, W = qkv.shape
+    hd = W // (n_heads + 2 * n_kv)
+    q, k, v = qkv.split([n_heads * hd, n_kv * hd, n_kv * hd], dim=-1)
+    q_oscale = (hd ** -0.5) * LOG2E if impl == "v3" else 1.0
+    q = rope(q.view(B, S, n_heads, hd), cos, sin, oscale=q_oscale)
+    k = rope(k.view(B, S, n_kv, hd), cos, sin)
+    v = v.view(B, S, n_kv, hd)
+    q, k, v = (t.transpose(1, 2) for t in (q, k, v))
+    return q, k, v, q_oscale
+
+
+class _QKVAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, n_heads, n_kv, impl):
+        B, S, _ = qkv.shape
+        q, k, v, q_oscale = _qkv_split_rope(qkv, cos, sin, n_heads, n_kv,
+                                            impl)
+        q, k, v, o, lse, scale = _attention_forward(
+            q, k, v, q.shape[-1] ** -0.5, impl)
+        ctx.save_for_backward(q, k, v, o, lse, cos, sin)
+        ctx.scale, ctx.q_oscale, ctx.n_kv = scale, q_oscale, n_kv
+        return o.transpose(1, 2).reshape(B, S, -1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, k, v, o, lse, cos, sin = ctx.saved_tensors
+        B, Hq, S, D = q.shape
+        # the [B,H,S,D] view of the [B,S,H*D] gradient goes in strided, the
+        # way o does: the dense backward wants it token-major anyway
+        grad_out = grad_out.reshape(B, S, Hq, D).transpose(1, 2)
+        dq, dk_e, dv_e = _attention_backward_expanded(
+            grad_out, q, k, v, o, lse, ctx.scale)
+        dqkv = attn_grad_pack(dq, dk_e, dv_e, cos, sin, ctx.n_kv,
+                              ctx.q_oscale)
+        return dqkv, None, None, None, None, None
+
+
+def qkv_attention(qkv, cos, sin, n_heads, n_kv, impl="ck"):
+    """Causal GQA attention block between the wqkv and wo GEMMs: qkv
+    [B, S, (n_heads + 2*n_kv)*D] (the wqkv output) -> o [B, S, n_heads*D].
+    Splits qkv, rotates q and k (impl="v3" folds scale*log2e into q) and runs
+    flash_attention's forward kernel; impl is "v3" or "ck".
+
+    As one autograd node its backward is the dense attention backward
+    followed by attn_grad_pack, which returns dqkv directly. KT_ATTN_PACK=0
+    runs the separate rope / flash_attention nodes instead; on CPU those
+    run with SDPA in place of the forward kernel."""
+    if impl not in ("v3", "ck"):
+        raise ValueError('impl must be "v3" or "ck"')
+    if qkv.dim() != 3 or qkv.shape[-1] % (n_heads + 2 * n_kv) \
+            or n_heads % n_kv:
+        raise ValueError("qkv must be [B, S, (n_heads + 2*n_kv)*D] with "
+                         "n_heads a multiple of n_kv")
+    if qkv.is_cuda and attn_pack_enabled():
+        return _QKVAttention.apply(qkv, cos, sin, n_heads, n_kv, impl)
+    B, S, _ = qkv.shape
+    q, k, v, _ = _qkv_split_rope(qkv, cos, sin, n_heads, n_kv, impl)
+    if qkv.is_cuda:
+        o = flash_attention(q, k, v, impl=impl)
+    else:
+        g = n_heads // n_kv
+        o = torch.nn.functional.scaled_dot_product_attention(
+            q, k.repeat_interleave(g, 1), v.repeat_interleave(g, 1),
+            is_causal=True,
+            scale=_LN2 if impl == "v3" else q.shape[-1] ** -0.5)
+    return o.transpose(1, 2).reshape(B, S, -1)
 
 
 # ---------------------------------------------------------------------------

@@ -23,6 +23,10 @@ void kt_rmsnorm_bwd(const void* dy, const void* ds, const void* x,
 void kt_rope(const void* x, void* o, const void* cost, const void* sint,
              long total_quads, int S, int Hh, int D, long src_t_stride,
              long src_h_stride, float sign, float oscale, hipStream_t stream);
+void kt_attn_grad_pack(const void* dq, const void* dk, const void* dv,
+                       void* out, const void* cost, const void* sint, long B,
+                       int S, int Hq, int Hkv, int D, const long* strides,
+                       float oscale, hipStream_t stream);
 void kt_swiglu_fwd(const void* gu, void* out, long N, int I,
                    hipStream_t stream);
 void kt_swiglu_bwd(const void* dout, const void* gu, void* dgu, long N, int I,
@@ -183,6 +187,61 @@ at::Tensor rope(const at::Tensor& x, const at::Tensor& cost,
           total_quads, (int)S, Hh, D, x.stride(0), x.stride(1), (float)sign,
           (float)oscale, cur_stream(x));
   return o;
+}
+
+at::Tensor attn_grad_pack(const at::Tensor& dq, const at::Tensor& dk_e,
+                          const at::Tensor& dv_e, const at::Tensor& cost,
+                          const at::Tensor& sint, int64_t n_kv,
+                          double q_oscale) {
+  // dq, dk_e, dv_e: [B, Hq, S, D] in any layout with a contiguous head dim
+  // ([B,H,S,D] buffers and transposed [B,S,H,D] buffers both go in as they
+  // are). Returns the packed [B, S, (Hq + 2*n_kv)*D] gradient of the qkv
+  // GEMM output. Every check is made before the launch.
+  TORCH_CHECK(dq.dim() == 4, "dq must be [B, Hq, S, D]");
+  TORCH_CHECK(dk_e.sizes() == dq.sizes() && dv_e.sizes() == dq.sizes(),
+              "dq, dk_e and dv_e must have the same shape");
+  const int64_t B = dq.size(0), Hq = dq.size(1), S = dq.size(2),
+                D = dq.size(3);
+  TORCH_CHECK(D > 0 && D % 8 == 0, "head dim must be a multiple of 8");
+  TORCH_CHECK(n_kv >= 1 && Hq % n_kv == 0, "Hq must be a multiple of n_kv");
+  long strides[9];
+  int si = 0;
+  for (const at::Tensor* t : {&dq, &dk_e, &dv_e}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kBFloat16,
+                "gradients must be bf16 GPU tensors");
+    TORCH_CHECK(t->device() == dq.device(), "gradients on different devices");
+    TORCH_CHECK(t->stride(3) == 1, "head dim must be contiguous");
+    for (int d = 0; d < 3; ++d) {
+      // a dim of size 1 is only ever indexed at 0: its stride is free
+      TORCH_CHECK(t->size(d) == 1 ||
+                      (t->stride(d) >= 0 && t->stride(d) % 8 == 0),
+                  "strides must be non-negative multiples of 8 elements");
+      strides[si++] = t->size(d) == 1 ? 0 : t->stride(d);
+    }
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "gradients must be 16 B aligned");
+  }
+  for (const at::Tensor* t : {&cost, &sint}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == dq.device() &&
+                    t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                    t->dim() == 2,
+                "cos/sin must be contiguous fp32 [>=S, D/2] GPU tables");
+    TORCH_CHECK(t->size(0) >= S && t->size(1) == D / 2, "cos/sin table shape");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "cos/sin must be 16 B aligned");
+  }
+  // the kernel keeps the position and the offset inside a token's row in int
+  TORCH_CHECK(S < (int64_t(1) << 31) &&
+                  (Hq + 2 * n_kv) * D < (int64_t(1) << 31),
+              "shape out of range");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dq.device());
+  auto out = at::empty({B, S, (Hq + 2 * n_kv) * D}, dq.options());
+  if (out.numel() == 0) return out;
+  kt_attn_grad_pack(dq.data_ptr(), dk_e.data_ptr(), dv_e.data_ptr(),
+                    out.data_ptr(), cost.data_ptr(), sint.data_ptr(), (long)B,
+                    (int)S, (int)Hq, (int)n_kv, (int)D, strides,
+                    (float)q_oscale, cur_stream(dq));
+  return out;
 }
 
 at::Tensor swiglu_fwd(const at::Tensor& gu) {
@@ -681,6 +740,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("x"), pybind11::arg("cost"), pybind11::arg("sint"),
           pybind11::arg("S"), pybind11::arg("sign"),
           pybind11::arg("oscale") = 1.0);
+  mod.def("attn_grad_pack", &attn_grad_pack,
+          "GQA group sum + RoPE^T + qkv packing of (dq, dk_exp, dv_exp)",
+          pybind11::arg("dq"), pybind11::arg("dk_e"), pybind11::arg("dv_e"),
+          pybind11::arg("cost"), pybind11::arg("sint"), pybind11::arg("n_kv"),
+          pybind11::arg("q_oscale"));
   mod.def("swiglu_fwd", &swiglu_fwd, "SwiGLU forward (bf16)");
   mod.def("swiglu_bwd", &swiglu_bwd, "SwiGLU backward (bf16)");
   mod.def("cross_entropy_fwd_", &cross_entropy_fwd_,

@@ -252,6 +252,105 @@ __global__ void rope_kernel(const u16* __restrict__ x, u16* __restrict__ o,
 }
 
 // ---------------------------------------------------------------------------
+// Attention backward epilogue: everything between the dense attention
+// backward and the wqkv GEMMs in one pass. dq, dk_e, dv_e are [B, Hq, S, D]
+// bf16 with explicit (batch, head, token) strides (dk_e/dv_e head-expanded,
+// expanded head h = kv head h / g); out is the packed [B*S, (Hq+2*Hkv)*D]
+// gradient of the qkv GEMM output:
+//   q head h   = oscale * R^T(dq[h])
+//   k head kv  = R^T(sum_j dk_e[kv*g + j])
+//   v head kv  = sum_j dv_e[kv*g + j]
+// R^T is rope_kernel's sign = -1 branch. Group sums, rotation and scale are
+// fp32 (sums in ascending j), one bf16 round per output element. A work item
+// is V elements of each half of one output head: V = 8 (16 B vectors) when
+// D % 16 == 0, else V = 4. Items run in output order, so stores are fully
+// coalesced and loads are too when the inputs are [B,S,H,D] buffers.
+// ---------------------------------------------------------------------------
+template <int V>
+__global__ void attn_grad_pack_kernel(
+    const u16* __restrict__ dq, const u16* __restrict__ dk,
+    const u16* __restrict__ dv, u16* __restrict__ out,
+    const float* __restrict__ cost, const float* __restrict__ sint,
+    long total_items, int S, int Hq, int Hkv, int D,
+    long q_sb, long q_sh, long q_ss, long k_sb, long k_sh, long k_ss,
+    long v_sb, long v_sh, long v_ss, float oscale) {
+  typedef ushort vecu __attribute__((ext_vector_type(V)));
+  const int half = D >> 1;
+  const int items_per_head = half / V;
+  const int g = Hq / Hkv;
+  const long items_per_tok = (long)(Hq + 2 * Hkv) * items_per_head;
+  for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < total_items;
+       it += (long)gridDim.x * blockDim.x) {
+    const long tok = it / items_per_tok;
+    const int rem = (int)(it - tok * items_per_tok);
+    const int oh = rem / items_per_head;
+    const int e = (rem - oh * items_per_head) * V;
+    const long b = tok / S;
+    const int pos = (int)(tok - b * S);
+    const u16* src;
+    long sh;
+    int n = g;
+    bool rot = true;
+    float sc = 1.f;
+    if (oh < Hq) {
+      src = dq + b * q_sb + (long)oh * q_sh + (long)pos * q_ss;
+      sh = q_sh;
+      n = 1;
+      sc = oscale;
+    } else if (oh < Hq + Hkv) {
+      src = dk + b * k_sb + (long)(oh - Hq) * g * k_sh + (long)pos * k_ss;
+      sh = k_sh;
+    } else {
+      src = dv + b * v_sb + (long)(oh - Hq - Hkv) * g * v_sh + (long)pos * v_ss;
+      sh = v_sh;
+      rot = false;
+    }
+    src += e;
+    float a[V], bb[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) a[i] = bb[i] = 0.f;
+    for (int j = 0; j < n; ++j, src += sh) {
+      // read once, never again: streaming loads
+      vecu x1 = __builtin_nontemporal_load(reinterpret_cast<const vecu*>(src));
+      vecu x2 =
+          __builtin_nontemporal_load(reinterpret_cast<const vecu*>(src + half));
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        a[i] += bf2f(x1[i]);
+        bb[i] += bf2f(x2[i]);
+      }
+    }
+    vecu o1, o2;
+    if (rot) {
+      const float* cp = cost + (size_t)pos * half + e;
+      const float* sp = sint + (size_t)pos * half + e;
+#pragma unroll
+      for (int i = 0; i < V; i += 4) {
+        vec4f c = *reinterpret_cast<const vec4f*>(cp + i);
+        vec4f s = *reinterpret_cast<const vec4f*>(sp + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          o1[i + k] = f2bf((a[i + k] * c[k] + bb[i + k] * s[k]) * sc);
+          o2[i + k] = f2bf((bb[i + k] * c[k] - a[i + k] * s[k]) * sc);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        o1[i] = f2bf(a[i]);
+        o2[i] = f2bf(bb[i]);
+      }
+    }
+    // Plain stores: the wqkv dgrad and wgrad GEMMs re-read dqkv at once.
+    // Streaming stores measured the same in the step (752.9 against 752.3
+    // ms, profiles/attn_backward_pack.md).
+    u16* op = out + ((size_t)tok * (Hq + 2 * Hkv) + oh) * D + e;
+    *reinterpret_cast<vecu*>(op) = o1;
+    *reinterpret_cast<vecu*>(op + half) = o2;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // SwiGLU: out = silu(gate) * up, with gate_up packed [N, 2I] from one GEMM.
 // ---------------------------------------------------------------------------
 __global__ void swiglu_fwd_kernel(const u16* __restrict__ gu,
@@ -658,6 +757,23 @@ void kt_rope(const void* x, void* o, const void* cost, const void* sint,
                      (const u16*)x, (u16*)o, (const float*)cost,
                      (const float*)sint, total_quads, S, Hh, D,
                      src_t_stride, src_h_stride, sign, oscale);
+}
+
+// strides: {batch, head, token} of dq, dk_e, dv_e, in elements
+void kt_attn_grad_pack(const void* dq, const void* dk, const void* dv,
+                       void* out, const void* cost, const void* sint, long B,
+                       int S, int Hq, int Hkv, int D, const long* strides,
+                       float oscale, hipStream_t stream) {
+  const int V = (D % 16 == 0) ? 8 : 4;
+  const long total = B * S * (long)(Hq + 2 * Hkv) * ((D >> 1) / V);
+  int grid = grid_for(total, 256);
+  auto kern = V == 8 ? attn_grad_pack_kernel<8> : attn_grad_pack_kernel<4>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, (const u16*)dq,
+                     (const u16*)dk, (const u16*)dv, (u16*)out,
+                     (const float*)cost, (const float*)sint, total, S, Hq,
+                     Hkv, D, strides[0], strides[1], strides[2], strides[3],
+                     strides[4], strides[5], strides[6], strides[7],
+                     strides[8], oscale);
 }
 
 void kt_swiglu_fwd(const void* gu, void* out, long N, int I,

@@ -7,13 +7,15 @@ on one GPU. Usage:
     python bench_decode.py --model llama3-8b --batch 8 --prompt 128 --new 128
     python bench_decode.py ... --kv paged [--page-size 16] [--num-splits 0]
     python bench_decode.py ... --kv paged --prefill paged
+    python bench_decode.py ... --kv paged --kv-dtype fp8
     python bench_decode.py ... --kv paged --prefix-cache --shared-prefix 2048
 
 --kv slot (default) is the padded slot cache; --kv paged the block-table
 page pools with the fused decode-attention kernel. --num-splits 0 lets the
 engine choose the split-KV factor. --prefill paged prefills straight into
 the pages with the paged prefill kernel; --prefix-cache shares prompt pages
-between requests. --shared-prefix N makes the first N prompt tokens the
+between requests. --kv-dtype fp8 stores the pages as e4m3 bytes (unit
+scales: random weights, nothing to calibrate on). --shared-prefix N makes the first N prompt tokens the
 same for every request and every run; one engine then serves the warm-up
 and the timed runs, so with --prefix-cache the timed run hits the pages the
 warm-up left. ttft_ms is the wall time of the first step() (all prefills
@@ -44,7 +46,8 @@ def build_model(name, dev):
 
 
 def make_engine(model, batch, prompt, new, kv="slot", page_size=16,
-                num_splits=0, prefill="cache", prefix_cache=False):
+                num_splits=0, prefill="cache", prefix_cache=False,
+                kv_dtype="bf16"):
     from kubetorch_amd.models import BatchedGenerator
 
     kw = {}
@@ -52,6 +55,8 @@ def make_engine(model, batch, prompt, new, kv="slot", page_size=16,
         kw = dict(kv=kv, page_size=page_size, num_splits=num_splits or None)
     if prefill != "cache" or prefix_cache:
         kw.update(prefill=prefill, prefix_cache=prefix_cache)
+    if kv_dtype == "fp8":
+        kw.update(kv_dtype="fp8")
     return BatchedGenerator(model, max_batch=batch, max_len=prompt + new + 8,
                             **kw)
 
@@ -105,12 +110,16 @@ def main():
                     help="paged: prefill into the pages (needs --kv paged)")
     ap.add_argument("--prefix-cache", action="store_true",
                     help="share prompt pages between requests (--kv paged)")
+    ap.add_argument("--kv-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="fp8: e4m3 page pools (needs --kv paged)")
     ap.add_argument("--shared-prefix", type=int, default=0,
                     help="first N prompt tokens equal across requests and "
                          "runs; one engine serves all runs")
     args = ap.parse_args()
     if not 0 <= args.shared_prefix <= args.prompt:
         ap.error("--shared-prefix must be in [0, --prompt]")
+    if args.kv_dtype == "fp8" and args.kv != "paged":
+        ap.error("--kv-dtype fp8 needs --kv paged")
 
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model, cfg = build_model(args.model, dev)
@@ -119,6 +128,8 @@ def main():
                 num_splits=args.num_splits)
     if args.prefill != "cache" or args.prefix_cache:
         mode.update(prefill=args.prefill, prefix_cache=args.prefix_cache)
+    if args.kv_dtype == "fp8":
+        mode.update(kv_dtype="fp8")
     extra = {}
     eng = None
     if args.shared_prefix:
@@ -140,6 +151,8 @@ def main():
                 "shared_prefix": args.shared_prefix}
         if eng is not None:
             more["hit_tokens"] = eng.prefix_stats["hit_tokens"] - hit0
+    if args.kv_dtype == "fp8":
+        more["kv_dtype"] = "fp8"
     print(json.dumps({
         "metric": "decode_tokens_per_sec",
         "value": round(new_toks / dt, 2),

@@ -34,11 +34,30 @@ class Generator:
                                   temperature=temperature)
         return out[0].tolist()
 
+    def generate_batch(self, prompts, max_new_tokens=16, kv_dtype=None):
+        """Continuous batching over the paged KV cache. kv_dtype="fp8"
+        keeps the pages as e4m3 bytes (half the KV memory and decode
+        reads), with scales calibrated on the first prompt."""
+        from kubetorch_amd.models import BatchedGenerator, calibrate_kv_scales
+
+        scales = None
+        if kv_dtype == "fp8":
+            scales = calibrate_kv_scales(self.model, prompts[0], margin=1.5)
+        eng = BatchedGenerator(self.model, max_batch=4, max_len=128,
+                               kv="paged", kv_dtype=kv_dtype,
+                               kv_scales=scales)
+        rids = [eng.submit(p, max_new_tokens=max_new_tokens) for p in prompts]
+        out = eng.run()
+        return [out[r] for r in rids]
+
 
 if __name__ == "__main__":
     gen = kt.cls(Generator).to(kt.Compute(gpus=0))  # gpus=1 on a cluster
     try:
         ids = gen.generate([1, 2, 3, 4], max_new_tokens=8)
         print("generated:", ids)
+        outs = gen.generate_batch([[1, 2, 3, 4], [9, 8, 7]], max_new_tokens=8,
+                                  kv_dtype="fp8")
+        print("generated (paged fp8 KV):", outs)
     finally:
         gen.teardown()

@@ -8,5 +8,8 @@ from kubetorch_amd.models.llama import (  # noqa: F401
     llama_tiny,
 )
 from kubetorch_amd.models.moe import MoEMLP, convert_to_moe  # noqa: F401
-from kubetorch_amd.models.paged_kv import PagedKVCache  # noqa: F401
+from kubetorch_amd.models.paged_kv import (  # noqa: F401
+    PagedKVCache,
+    calibrate_kv_scales,
+)
 from kubetorch_amd.models.serving import BatchedGenerator  # noqa: F401

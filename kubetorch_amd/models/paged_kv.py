@@ -24,6 +24,12 @@ stay cached on an LRU list until the allocator needs them; evicting a node
 drops its whole subtree from the trie, so no unreachable page stays
 registered and a page reused for other content cannot be hit through an
 old path.
+
+kv_dtype="fp8" (opt-in) allocates the pools as torch.float8_e4m3fn, one
+byte per element, with static fp32 scales per layer and kv head: a byte
+encodes x / scale (ops.paged_kv_write quantises, the attention ops
+dequantise). Pages are bytes to everything above, so none of it changes.
+calibrate_kv_scales derives scales from one prompt.
 """
 from collections import OrderedDict
 
@@ -40,15 +46,46 @@ class _Node:
         self.children = {}
 
 
+def _host_scales(scales, cfg, name):
+    """[n_layers, n_kv] fp32 on the host, positive and finite; None = ones."""
+    shape = (cfg.n_layers, cfg.n_kv_heads)
+    if scales is None:
+        return torch.ones(shape, dtype=torch.float32)
+    s = torch.as_tensor(scales).detach().to("cpu", torch.float32)
+    if tuple(s.shape) != shape:
+        raise ValueError(f"{name} must be [n_layers, n_kv] = {list(shape)}, "
+                         f"got {list(s.shape)}")
+    if not bool(((s > 0) & s.isfinite()).all()):
+        raise ValueError(f"{name} must be positive and finite")
+    return s
+
+
 class PagedKVCache:
     def __init__(self, cfg, num_pages, page_size, max_batch, max_blocks,
-                 device, dtype, prefix_cache=False):
+                 device, dtype, prefix_cache=False, kv_dtype=None,
+                 k_scales=None, v_scales=None):
         if num_pages < 1 or max_blocks < 1 or max_batch < 1:
             raise ValueError("num_pages, max_blocks and max_batch must be >= 1")
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype must be None or 'fp8', got {kv_dtype!r}")
+        if kv_dtype is None and (k_scales is not None or v_scales is not None):
+            raise ValueError("k_scales/v_scales need kv_dtype='fp8'")
         self.num_pages = num_pages
         self.page_size = page_size
         self.max_batch = max_batch
         self.max_blocks = max_blocks
+        self.kv_dtype = kv_dtype
+        # kv_dtype="fp8": one-byte e4m3 pages (the allocator below deals in
+        # pages, not bytes, and is the same) and static per-layer [n_kv]
+        # fp32 scales on the device, which ops.paged_* take; None otherwise
+        self.k_scale = [None] * cfg.n_layers
+        self.v_scale = [None] * cfg.n_layers
+        if kv_dtype == "fp8":
+            dtype = torch.float8_e4m3fn
+            ks = _host_scales(k_scales, cfg, "k_scales").to(device)
+            vs = _host_scales(v_scales, cfg, "v_scales").to(device)
+            self.k_scale = list(ks.unbind(0))
+            self.v_scale = list(vs.unbind(0))
         shape = (num_pages, cfg.n_kv_heads, page_size, cfg.head_dim)
         self.k = [torch.zeros(shape, device=device, dtype=dtype)
                   for _ in range(cfg.n_layers)]
@@ -208,3 +245,37 @@ class PagedKVCache:
         self._owned[slot] = []
         self._host_table[slot].fill_(-1)
         self.block_table[slot].copy_(self._host_table[slot])
+
+
+@torch.no_grad()
+def calibrate_kv_scales(model, tokens, margin=1.0):
+    """Static fp8 scales from one prompt: (k_scales, v_scales), each
+    [n_layers, n_kv] fp32 = max(amax, tiny) * margin / 448, where amax is
+    the largest |k| (after RoPE) or |v| of that layer and kv head over the
+    prompt `tokens` ([S] or [1, S] ids).
+
+    With scale 1.0 everything below 2^-6 lands in e4m3's subnormals (step
+    2^-9), which V activations commonly do; a calibrated scale puts the
+    observed range at the top of the format. Values beyond the calibrated
+    amax saturate at +-448 * scale (the write clamps)."""
+    from kubetorch_amd import ops
+
+    cfg = model.cfg
+    tokens = torch.as_tensor(tokens, device=model.embed.weight.device)
+    tokens = tokens.reshape(1, -1).long()
+    S = tokens.shape[1]
+    k_amax = torch.zeros(cfg.n_layers, cfg.n_kv_heads)
+    v_amax = torch.zeros(cfg.n_layers, cfg.n_kv_heads)
+    cos, sin = model.rope_cos[:S], model.rope_sin[:S]
+
+    def attend(i, layer, q, k, v):
+        # q [1, S, Hq, hd], k / v [1, S, n_kv, hd]
+        k_amax[i] = k.float().abs().amax((0, 1, 3)).cpu()
+        v_amax[i] = v.float().abs().amax((0, 1, 3)).cpu()
+        o = layer.attn._sdpa(q.transpose(1, 2), k.transpose(1, 2),
+                             v.transpose(1, 2), causal=True)
+        return o.transpose(1, 2).reshape(1, S, -1)
+
+    model._walk(model.embed(tokens), lambda x: ops.rope(x, cos, sin), attend)
+    tiny = torch.finfo(torch.float32).tiny
+    return tuple(a.clamp_min(tiny) * (margin / 448.0) for a in (k_amax, v_amax))

@@ -30,6 +30,13 @@ an earlier request's prompt for a new prompt that starts with the same
 tokens (models/paged_kv.py); only the rest of the prompt is computed.
 Lookup precedes publication, so requests admitted in the same step() do
 not share pages with each other.
+
+`kv_dtype="fp8"` (opt-in, needs kv="paged") keeps the pages as e4m3 bytes
+with static fp32 scales per layer and kv head (`kv_scales`, see
+models/paged_kv.py): every place that touches pages passes the layer's
+scales to the paged ops, which quantise on write and dequantise on read.
+Half the KV bytes per token; the allocator and the prefix cache are the
+same.
 """
 from dataclasses import dataclass, field
 
@@ -54,9 +61,17 @@ class BatchedGenerator:
     def __init__(self, model, max_batch=8, max_len=None, device=None,
                  prefill_chunk=None, graph=None, kv="slot", page_size=16,
                  num_pages=None, num_splits=None, prefill="cache",
-                 prefix_cache=False):
+                 prefix_cache=False, kv_dtype=None, kv_scales=None):
         if kv not in ("slot", "paged"):
             raise ValueError(f"kv must be 'slot' or 'paged', got {kv!r}")
+        if kv_dtype not in (None, "fp8"):
+            raise ValueError(f"kv_dtype must be None or 'fp8', got {kv_dtype!r}")
+        if kv_dtype == "fp8" and kv != "paged":
+            raise ValueError("kv_dtype='fp8' needs kv='paged'")
+        if kv_scales is not None and kv_dtype != "fp8":
+            raise ValueError("kv_scales need kv_dtype='fp8'")
+        k_scales, v_scales = kv_scales if kv_scales is not None \
+            else (None, None)
         if prefill not in ("cache", "paged"):
             raise ValueError(
                 f"prefill must be 'cache' or 'paged', got {prefill!r}")
@@ -84,6 +99,8 @@ class BatchedGenerator:
             # the paged HIP kernels; no slot slabs are allocated. The
             # default pool has the slot cache's capacity, so admission
             # never waits for pages; a smaller num_pages makes it wait.
+            # kv_dtype="fp8" keeps that default: the same token capacity
+            # in half the bytes (pass a larger num_pages to spend them).
             from kubetorch_amd.models.paged_kv import PagedKVCache
 
             max_blocks = -(-self.max_len // page_size)
@@ -91,7 +108,9 @@ class BatchedGenerator:
                 num_pages = max_batch * max_blocks
             self._pkv = PagedKVCache(cfg, num_pages, page_size, max_batch,
                                      max_blocks, self.device, self.dtype,
-                                     prefix_cache=self._prefix)
+                                     prefix_cache=self._prefix,
+                                     kv_dtype=kv_dtype, k_scales=k_scales,
+                                     v_scales=v_scales)
             # fixed for the engine's life so the decode grid is static
             # (one captured graph serves every horizon)
             self._num_splits = num_splits or ops.paged_num_splits(
@@ -244,10 +263,12 @@ class BatchedGenerator:
         slot_map = torch.tensor(self._pkv.token_slots(req.slot, 0, S0),
                                 dtype=torch.int32).to(self.device)
         for i in range(self.cfg.n_layers):
-            # [n_kv, S0, hd] -> [S0, n_kv, hd] views, no copy
+            # [n_kv, S0, hd] -> [S0, n_kv, hd] views, no copy; fp8 pools
+            # quantise the rows on their way in (scales None otherwise)
             ops.paged_kv_write(cache.k[i][j, :, :S0].transpose(0, 1),
                                cache.v[i][j, :, :S0].transpose(0, 1),
-                               self._pkv.k[i], self._pkv.v[i], slot_map)
+                               self._pkv.k[i], self._pkv.v[i], slot_map,
+                               self._pkv.k_scale[i], self._pkv.v_scale[i])
 
     def _prefill_packed(self, reqs):
         """Prefill every admitted request in packed forwards over the pages:
@@ -310,9 +331,11 @@ class BatchedGenerator:
 
         def attend(i, layer, q, k, v):
             kp, vp = self._pkv.k[i], self._pkv.v[i]
-            ops.paged_kv_write(k[0], v[0], kp, vp, slot_map)
+            ks, vs = self._pkv.k_scale[i], self._pkv.v_scale[i]
+            ops.paged_kv_write(k[0], v[0], kp, vp, slot_map, ks, vs)
             o = ops.paged_attention_prefill(q[0], kp, vp, table, cu,
-                                            seq_lens, max_q)
+                                            seq_lens, max_q, k_scale=ks,
+                                            v_scale=vs)
             return o.reshape(1, T, -1)
 
         h = m._walk(m.embed(toks.view(1, T)),
@@ -404,9 +427,11 @@ class BatchedGenerator:
 
         def attend(i, layer, q, k, v):
             kp, vp = self._pkv.k[i], self._pkv.v[i]
-            ops.paged_kv_write(k[:, 0], v[:, 0], kp, vp, slot_map)
+            ks, vs = self._pkv.k_scale[i], self._pkv.v_scale[i]
+            ops.paged_kv_write(k[:, 0], v[:, 0], kp, vp, slot_map, ks, vs)
             o = ops.paged_attention_decode(q[:, 0], kp, vp, table, seq_lens,
-                                           num_splits=self._num_splits)
+                                           num_splits=self._num_splits,
+                                           k_scale=ks, v_scale=vs)
             return o.reshape(B, 1, -1)
 
         return self._decode_walk(toks, lens, attend)

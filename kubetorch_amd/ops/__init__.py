@@ -10,6 +10,7 @@ Dispatch policy:
 """
 import importlib.util
 import os
+import weakref
 
 import torch
 
@@ -596,15 +597,99 @@ def _check_pools(k_pages, v_pages):
         raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS}")
 
 
-def paged_kv_write(k_new, v_new, k_pages, v_pages, slot_mapping):
+# fp8 pools: the same layout with torch.float8_e4m3fn (OCP e4m3) elements
+# and static fp32 scales per kv head, k_scale / v_scale [n_kv] on the pools'
+# device (None = 1.0). A stored byte encodes x / scale, the value read back
+# is float(byte) * scale. The kernels read the scales from device memory:
+# no host sync, capturable.
+PAGED_FP8 = torch.float8_e4m3fn
+PAGED_FP8_MAX = 448.0
+_FLOAT8_DTYPES = tuple(getattr(torch, n) for n in (
+    "float8_e4m3fn", "float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz")
+    if hasattr(torch, n))
+
+
+def _fp8_pools(k_pages, v_pages, k_scale, v_scale):
+    """True for a pair of e4m3 pools (the fp8 path), False for unquantised
+    pools (the code as it was). One fp8 pool next to another dtype, an
+    e5m2 or fnuz pool, and scales without fp8 pools raise."""
+    kd, vd = k_pages.dtype, v_pages.dtype
+    if kd == PAGED_FP8 and vd == PAGED_FP8:
+        return True
+    if kd in _FLOAT8_DTYPES or vd in _FLOAT8_DTYPES:
+        raise ValueError("8-bit pools must both be torch.float8_e4m3fn, got "
+                         f"{kd} and {vd}")
+    if k_scale is not None or v_scale is not None:
+        raise ValueError("k_scale/v_scale are for float8_e4m3fn pools only")
+    return False
+
+
+def _fp8_scales(k_pages, k_scale, v_scale):
+    """The two [n_kv] fp32 scale tensors of an fp8 pool pair, None replaced
+    by ones. Shape, dtype and device are checked everywhere; the values
+    (positive, finite) only on the CPU, where looking is no device sync."""
+    n_kv = k_pages.shape[1] if k_pages.dim() == 4 else -1
+    out = []
+    for name, s in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if s is None:
+            s = torch.ones(max(n_kv, 0), dtype=torch.float32,
+                           device=k_pages.device)
+        if not torch.is_tensor(s) or s.dtype != torch.float32 \
+                or tuple(s.shape) != (n_kv,) or s.device != k_pages.device:
+            raise ValueError(f"{name} must be [n_kv] fp32 on the pools' "
+                             "device")
+        if not s.is_cuda and not bool(((s > 0) & s.isfinite()).all()):
+            raise ValueError(f"{name} must be positive and finite")
+        out.append(s.contiguous())
+    return out
+
+
+_INV_SCALES = {}   # id(scale) -> (weakref, version, 1/scale)
+
+
+def _inv_scale(s):
+    """s.reciprocal(), kept per scale tensor while it lives and is not
+    written in place: the serving engine passes the same static scales in
+    every step of every layer, and two more launches per paged_kv_write
+    cost a decode step more than the fp8 read saves it."""
+    key = id(s)
+    hit = _INV_SCALES.get(key)
+    if hit is not None and hit[0]() is s and hit[1] == s._version:
+        return hit[2]
+    inv = s.reciprocal()
+    if s.is_cuda and torch.cuda.is_current_stream_capturing():
+        return inv  # lives in the graph's memory pool: not kept
+    _INV_SCALES[key] = (weakref.ref(s, lambda _: _INV_SCALES.pop(key, None)),
+                        s._version, inv)
+    return inv
+
+
+def _fp8_quantize_ref(x, inv_scale):
+    """[T, n_kv, hd] -> e4m3: one fp32 multiply by the head's 1/scale, clamp
+    to the finite range, round to nearest even. NaN stays NaN, +-inf
+    saturate. The kernel's bytes equal this."""
+    y = x.float() * inv_scale.view(1, -1, 1)
+    return y.clamp(-PAGED_FP8_MAX, PAGED_FP8_MAX).to(PAGED_FP8)
+
+
+def paged_kv_write(k_new, v_new, k_pages, v_pages, slot_mapping,
+                   k_scale=None, v_scale=None):
     """Scatter k_new/v_new [T, n_kv, hd] into the page pools in place.
 
     slot_mapping [T] int32 holds each token's flat physical index
     page*page_size + offset; a negative entry writes nothing. The result is
-    bitwise what a torch indexed copy gives."""
+    bitwise what a torch indexed copy gives. Into float8_e4m3fn pools the
+    rows are quantised with k_scale/v_scale ([n_kv] fp32, None = 1.0):
+    bitwise _fp8_quantize_ref."""
     _no_grad_inputs("paged_kv_write", k_new, v_new, k_pages, v_pages)
+    fp8 = _fp8_pools(k_pages, v_pages, k_scale, v_scale)
+    k_inv = v_inv = None
+    if fp8:
+        k_inv, v_inv = (_inv_scale(s) for s in
+                        _fp8_scales(k_pages, k_scale, v_scale))
     if k_pages.is_cuda:
-        _ext().paged_kv_write(k_new, v_new, k_pages, v_pages, slot_mapping)
+        _ext().paged_kv_write(k_new, v_new, k_pages, v_pages, slot_mapping,
+                              k_inv, v_inv)
         return
     _check_pools(k_pages, v_pages)
     P, Hkv, ps, hd = k_pages.shape
@@ -617,6 +702,14 @@ def paged_kv_write(k_new, v_new, k_pages, v_pages, slot_mapping):
     slots = slot_mapping.long()
     keep = (slots >= 0) & (slots < P * ps)
     page, off = slots[keep] // ps, slots[keep] % ps
+    if fp8:
+        if k_new.dtype not in (torch.bfloat16, torch.float32) \
+                or v_new.dtype != k_new.dtype:
+            raise ValueError("k_new/v_new must be bf16 (fp32 on the CPU "
+                             "reference path)")
+        k_pages[page, :, off] = _fp8_quantize_ref(k_new[keep], k_inv)
+        v_pages[page, :, off] = _fp8_quantize_ref(v_new[keep], v_inv)
+        return
     k_pages[page, :, off] = k_new[keep].to(k_pages.dtype)
     v_pages[page, :, off] = v_new[keep].to(v_pages.dtype)
 
@@ -647,7 +740,15 @@ def paged_num_splits(batch, n_kv, max_tokens):
     return max(1, min(want, cap, _PAGED_MAX_SPLITS))
 
 
-def _paged_attention_ref(q, k_pages, v_pages, block_table, seq_lens, scale):
+def _dequant(rows, kv_scale):
+    """Gathered pool rows [n, Hkv, hd] -> fp32 [Hkv, n, hd]; fp8 rows are
+    multiplied by their kv head's scale (kv_scale [Hkv], None otherwise)."""
+    x = rows.float().transpose(0, 1)
+    return x if kv_scale is None else x * kv_scale.view(-1, 1, 1)
+
+
+def _paged_attention_ref(q, k_pages, v_pages, block_table, seq_lens, scale,
+                         k_scale=None, v_scale=None):
     """fp32 reference: per sequence, gather the valid tokens through the
     block table and run softmax(q k^T scale) v. Pages that are not
     referenced and positions >= seq_len are never indexed."""
@@ -666,8 +767,8 @@ def _paged_attention_ref(q, k_pages, v_pages, block_table, seq_lens, scale):
             continue
         page = torch.tensor([p for p, _ in toks], device=q.device)
         off = torch.tensor([o for _, o in toks], device=q.device)
-        k = k_pages[page, :, off].float().transpose(0, 1)   # [Hkv, n, hd]
-        v = v_pages[page, :, off].float().transpose(0, 1)
+        k = _dequant(k_pages[page, :, off], k_scale)        # [Hkv, n, hd]
+        v = _dequant(v_pages[page, :, off], v_scale)
         qb = q[b].float().view(Hkv, g, hd)
         p = torch.softmax(torch.matmul(qb, k.transpose(1, 2)) * scale, dim=-1)
         out[b] = torch.matmul(p, v).view(Hq, hd)
@@ -675,7 +776,8 @@ def _paged_attention_ref(q, k_pages, v_pages, block_table, seq_lens, scale):
 
 
 def paged_attention_decode(q, k_pages, v_pages, block_table, seq_lens,
-                           scale=None, num_splits=0):
+                           scale=None, num_splits=0, k_scale=None,
+                           v_scale=None):
     """Single-token GQA attention over a block-table paged KV cache.
 
     q [B, Hq, hd]; block_table [B, max_blocks] int32 (-1 = unused);
@@ -683,8 +785,12 @@ def paged_attention_decode(q, k_pages, v_pages, block_table, seq_lens,
     written; a row with seq_lens 0 gives zeros. Reads are proportional to
     each row's own length. num_splits=0 picks a split-KV factor from the
     table's capacity (paged_num_splits); any fixed value gives the same
-    result up to fp32 merge rounding."""
+    result up to fp32 merge rounding. The pools share q's dtype, or are
+    both float8_e4m3fn with k_scale/v_scale [n_kv] fp32 (None = 1.0)."""
     _no_grad_inputs("paged_attention_decode", q, k_pages, v_pages)
+    fp8 = _fp8_pools(k_pages, v_pages, k_scale, v_scale)
+    if fp8:
+        k_scale, v_scale = _fp8_scales(k_pages, k_scale, v_scale)
     if scale is None:
         scale = q.shape[-1] ** -0.5
     if num_splits == 0 and k_pages.dim() == 4 and block_table.dim() == 2 \
@@ -695,14 +801,18 @@ def paged_attention_decode(q, k_pages, v_pages, block_table, seq_lens,
     if q.is_cuda:
         return _ext().paged_attention_decode(q, k_pages, v_pages, block_table,
                                              seq_lens, float(scale),
-                                             int(num_splits))
+                                             int(num_splits), k_scale,
+                                             v_scale)
     _check_pools(k_pages, v_pages)
     if q.dim() != 3 or q.shape[2] != k_pages.shape[3]:
         raise ValueError("q must be [B, Hq, hd] with the pool's head_dim")
     Hq, Hkv = q.shape[1], k_pages.shape[1]
     if Hq % Hkv or Hq // Hkv not in PAGED_GROUPS:
         raise ValueError(f"group Hq/Hkv must be one of {PAGED_GROUPS}")
-    if q.dtype != k_pages.dtype or q.dtype != v_pages.dtype:
+    if fp8:
+        if q.dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError("q must be bf16 (fp32 on the CPU reference path)")
+    elif q.dtype != k_pages.dtype or q.dtype != v_pages.dtype:
         raise ValueError("q and the pools must share a dtype")
     if block_table.dtype != torch.int32 or seq_lens.dtype != torch.int32 \
             or block_table.dim() != 2 or block_table.shape[0] != q.shape[0] \
@@ -712,11 +822,11 @@ def paged_attention_decode(q, k_pages, v_pages, block_table, seq_lens,
     if num_splits < 1:
         raise ValueError("num_splits must be >= 0")
     return _paged_attention_ref(q, k_pages, v_pages, block_table, seq_lens,
-                                float(scale))
+                                float(scale), k_scale, v_scale)
 
 
 def _paged_prefill_ref(q, k_pages, v_pages, block_table, cu_q_lens, seq_lens,
-                       scale):
+                       scale, k_scale=None, v_scale=None):
     """fp32 reference of paged_attention_prefill: per row, gather the keys
     the row's query tokens may attend through the block table and run an
     offset-causal softmax. Keys behind table entries outside [0, P) are
@@ -747,8 +857,8 @@ def _paged_prefill_ref(q, k_pages, v_pages, block_table, cu_q_lens, seq_lens,
         page = torch.tensor([p if 0 <= p < P else 0 for p in pages],
                             device=q.device)
         off = torch.arange(n, device=q.device) % ps
-        k = k_pages[page, :, off].float().transpose(0, 1)   # [Hkv, n, hd]
-        v = v_pages[page, :, off].float().transpose(0, 1)
+        k = _dequant(k_pages[page, :, off], k_scale)        # [Hkv, n, hd]
+        v = _dequant(v_pages[page, :, off], v_scale)
         k = torch.where(ok.view(1, n, 1), k, torch.zeros_like(k))
         v = torch.where(ok.view(1, n, 1), v, torch.zeros_like(v))
         ti = torch.tensor([t for t, _ in toks], device=q.device)
@@ -768,7 +878,8 @@ def _paged_prefill_ref(q, k_pages, v_pages, block_table, cu_q_lens, seq_lens,
 
 
 def paged_attention_prefill(q, k_pages, v_pages, block_table, cu_q_lens,
-                            seq_lens, max_q_len, scale=None):
+                            seq_lens, max_q_len, scale=None, k_scale=None,
+                            v_scale=None):
     """Causal GQA attention of a packed, variable-length batch of query
     tokens over a block-table paged KV cache.
 
@@ -780,15 +891,19 @@ def paged_attention_prefill(q, k_pages, v_pages, block_table, cu_q_lens,
     query count. Token i of row b sits at position seq_lens[b] - qlen_b + i
     and attends keys [0, position]. Returns [T, Hq, hd]; a row with
     qlen_b > seq_lens[b], tokens at a position >= max_blocks*page_size and
-    tokens of no row are zero."""
+    tokens of no row are zero. The pools share q's dtype, or are both
+    float8_e4m3fn with k_scale/v_scale [n_kv] fp32 (None = 1.0)."""
     _no_grad_inputs("paged_attention_prefill", q, k_pages, v_pages)
+    fp8 = _fp8_pools(k_pages, v_pages, k_scale, v_scale)
+    if fp8:
+        k_scale, v_scale = _fp8_scales(k_pages, k_scale, v_scale)
     if scale is None:
         scale = q.shape[-1] ** -0.5
     if q.is_cuda:
         return _ext().paged_attention_prefill(q, k_pages, v_pages,
                                               block_table, cu_q_lens,
                                               seq_lens, int(max_q_len),
-                                              float(scale))
+                                              float(scale), k_scale, v_scale)
     _check_pools(k_pages, v_pages)
     if q.dim() != 3 or q.shape[2] != k_pages.shape[3]:
         raise ValueError("q must be [T, Hq, hd] with the pool's head_dim")
@@ -797,7 +912,7 @@ def paged_attention_prefill(q, k_pages, v_pages, block_table, cu_q_lens,
         raise ValueError(f"group Hq/Hkv must be one of {PAGED_GROUPS}")
     if q.dtype != torch.bfloat16 and q.dtype != torch.float32:
         raise ValueError("q must be bf16 (fp32 on the CPU reference path)")
-    if q.dtype != k_pages.dtype or q.dtype != v_pages.dtype:
+    if not fp8 and (q.dtype != k_pages.dtype or q.dtype != v_pages.dtype):
         raise ValueError("q and the pools must share a dtype")
     if block_table.dtype != torch.int32 or block_table.dim() != 2:
         raise ValueError("block_table must be [B, max_blocks] int32")
@@ -811,7 +926,7 @@ def paged_attention_prefill(q, k_pages, v_pages, block_table, cu_q_lens,
     if not 0 < scale < float("inf"):
         raise ValueError("scale must be positive and finite")
     return _paged_prefill_ref(q, k_pages, v_pages, block_table, cu_q_lens,
-                              seq_lens, float(scale))
+                              seq_lens, float(scale), k_scale, v_scale)
 
 
 # ---------------------------------------------------------------------------

@@ -68,20 +68,29 @@ void kt_paged_kv_write(const void* k_new, const void* v_new, void* k_pages,
                        int Hkv, int hd, int page_size, long num_pages,
                        long k_st, long k_sh, long v_st, long v_sh,
                        hipStream_t stream);
+void kt_paged_kv_write_fp8(const void* k_new, const void* v_new,
+                           void* k_pages, void* v_pages,
+                           const void* slot_mapping, const void* k_inv,
+                           const void* v_inv, long T, int Hkv, int hd,
+                           int page_size, long num_pages, long k_st,
+                           long k_sh, long v_st, long v_sh,
+                           hipStream_t stream);
 int kt_paged_attention_decode(const void* q, const void* k_pages,
                               const void* v_pages, const void* block_table,
                               const void* seq_lens, void* out, void* po,
                               void* pm, void* pl, int B, int Hq, int Hkv,
                               int hd, int page_size, int num_pages,
                               int max_blocks, int num_splits, float scale,
-                              hipStream_t stream);
+                              int fp8, const void* k_scale,
+                              const void* v_scale, hipStream_t stream);
 int kt_paged_attention_prefill(const void* q, const void* k_pages,
                                const void* v_pages, const void* block_table,
                                const void* cu_q_lens, const void* seq_lens,
                                void* out, long T, long q_st, long q_sh, int B,
                                int Hq, int Hkv, int hd, int page_size,
                                int num_pages, int max_blocks, int max_q_len,
-                               float scale, hipStream_t stream);
+                               float scale, int fp8, const void* k_scale,
+                               const void* v_scale, hipStream_t stream);
 }
 
 namespace {
@@ -534,10 +543,38 @@ void transpose_segments_bf16(const at::Tensor& flat_src, at::Tensor flat_dst,
                              cur_stream(flat_src));
 }
 
-// Shared checks of a paged KV pool pair [num_pages, n_kv, page_size, hd].
-void check_page_pools(const at::Tensor& k_pages, const at::Tensor& v_pages) {
-  CHECK_BF16_CONTIG(k_pages);
-  CHECK_BF16_CONTIG(v_pages);
+// Shared checks of a paged KV pool pair [num_pages, n_kv, page_size, hd]:
+// both bf16, or both OCP e4m3 (returns true) with per-kv-head scales.
+// `scales` are the op's k_scale and v_scale, or its k and v inverse scales:
+// [n_kv] fp32 on the pools' device, given exactly when the pools are fp8.
+// Their values are not looked at (that would be a device sync).
+bool check_page_pools(const at::Tensor& k_pages, const at::Tensor& v_pages,
+                      const c10::optional<at::Tensor>& k_scale,
+                      const c10::optional<at::Tensor>& v_scale) {
+  const bool fp8 = k_pages.scalar_type() == at::kFloat8_e4m3fn;
+  if (fp8) {
+    TORCH_CHECK(k_pages.is_cuda() && v_pages.is_cuda(),
+                "k_pages/v_pages must be on GPU");
+    TORCH_CHECK(v_pages.scalar_type() == at::kFloat8_e4m3fn,
+                "k_pages is float8_e4m3fn, v_pages is not");
+    TORCH_CHECK(k_pages.is_contiguous() && v_pages.is_contiguous(),
+                "k_pages/v_pages must be contiguous");
+    for (const auto* s : {&k_scale, &v_scale}) {
+      TORCH_CHECK(s->has_value(), "fp8 pools need k and v scales");
+      const at::Tensor& t = s->value();
+      TORCH_CHECK(t.is_cuda() && t.device() == k_pages.device() &&
+                      t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                      t.dim() == 1 && k_pages.dim() == 4 &&
+                      t.size(0) == k_pages.size(1),
+                  "k/v scales must be [n_kv] contiguous fp32 on the pools' "
+                  "device");
+    }
+  } else {
+    CHECK_BF16_CONTIG(k_pages);
+    CHECK_BF16_CONTIG(v_pages);
+    TORCH_CHECK(!k_scale.has_value() && !v_scale.has_value(),
+                "k/v scales are for float8_e4m3fn pools only");
+  }
   TORCH_CHECK(k_pages.dim() == 4, "k_pages must be [pages, n_kv, page, hd]");
   TORCH_CHECK(v_pages.sizes() == k_pages.sizes(), "k/v pool shape mismatch");
   TORCH_CHECK(v_pages.device() == k_pages.device(), "k/v pool device");
@@ -547,15 +584,23 @@ void check_page_pools(const at::Tensor& k_pages, const at::Tensor& v_pages) {
   TORCH_CHECK(hd == 64 || hd == 128, "head_dim must be 64 or 128, got ", hd);
   TORCH_CHECK(k_pages.size(0) * ps < (int64_t)INT32_MAX,
               "num_pages*page_size must fit int32");
+  return fp8;
+}
+
+const void* scale_ptr(const c10::optional<at::Tensor>& s) {
+  return s.has_value() ? s->data_ptr() : nullptr;
 }
 
 void paged_kv_write(const at::Tensor& k_new, const at::Tensor& v_new,
                     at::Tensor k_pages, at::Tensor v_pages,
-                    const at::Tensor& slot_mapping) {
+                    const at::Tensor& slot_mapping,
+                    const c10::optional<at::Tensor>& k_inv_scale,
+                    const c10::optional<at::Tensor>& v_inv_scale) {
   // k_new / v_new: [T, n_kv, hd] bf16, token and head dims may be strided
   // (qkv-split views, prefill-cache views); slot_mapping: [T] int32 flat
   // physical token index page*page_size + offset, negative = write nothing.
-  check_page_pools(k_pages, v_pages);
+  // fp8 pools: k_inv_scale / v_inv_scale [n_kv] fp32 hold 1/scale.
+  const bool fp8 = check_page_pools(k_pages, v_pages, k_inv_scale, v_inv_scale);
   const int Hkv = (int)k_pages.size(1), ps = (int)k_pages.size(2);
   const int hd = (int)k_pages.size(3);
   for (const at::Tensor* t : {&k_new, &v_new}) {
@@ -580,6 +625,15 @@ void paged_kv_write(const at::Tensor& k_new, const at::Tensor& v_new,
               "slot_mapping must be [T] contiguous int32 on the pool's device");
   if (T == 0) return;
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(k_pages.device());
+  if (fp8) {
+    kt_paged_kv_write_fp8(
+        k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(),
+        v_pages.data_ptr(), slot_mapping.data_ptr(), scale_ptr(k_inv_scale),
+        scale_ptr(v_inv_scale), (long)T, Hkv, hd, ps, (long)k_pages.size(0),
+        k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1),
+        cur_stream(k_pages));
+    return;
+  }
   kt_paged_kv_write(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(),
                     v_pages.data_ptr(), slot_mapping.data_ptr(), (long)T, Hkv,
                     hd, ps, (long)k_pages.size(0), k_new.stride(0),
@@ -592,11 +646,13 @@ at::Tensor paged_attention_decode(const at::Tensor& q,
                                   const at::Tensor& v_pages,
                                   const at::Tensor& block_table,
                                   const at::Tensor& seq_lens, double scale,
-                                  int64_t num_splits) {
+                                  int64_t num_splits,
+                                  const c10::optional<at::Tensor>& k_scale,
+                                  const c10::optional<at::Tensor>& v_scale) {
   // q: [B, Hq, hd]; block_table: [B, max_blocks] int32 (-1 = unused);
   // seq_lens: [B] int32 valid tokens per row (0 = inactive, zero output).
   CHECK_BF16_CONTIG(q);
-  check_page_pools(k_pages, v_pages);
+  const bool fp8 = check_page_pools(k_pages, v_pages, k_scale, v_scale);
   const int64_t num_pages = k_pages.size(0);
   const int Hkv = (int)k_pages.size(1), ps = (int)k_pages.size(2);
   const int hd = (int)k_pages.size(3);
@@ -644,7 +700,8 @@ at::Tensor paged_attention_decode(const at::Tensor& q,
       q.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(),
       block_table.data_ptr(), seq_lens.data_ptr(), out.data_ptr(), po_p, pm_p,
       pl_p, (int)B, (int)Hq, Hkv, hd, ps, (int)num_pages, (int)max_blocks,
-      (int)num_splits, (float)scale, cur_stream(q));
+      (int)num_splits, (float)scale, (int)fp8, scale_ptr(k_scale),
+      scale_ptr(v_scale), cur_stream(q));
   TORCH_CHECK(rc == 0, "paged_attention_decode: no kernel for head_dim ", hd,
               " group ", G);
   return out;
@@ -656,13 +713,15 @@ at::Tensor paged_attention_prefill(const at::Tensor& q,
                                    const at::Tensor& block_table,
                                    const at::Tensor& cu_q_lens,
                                    const at::Tensor& seq_lens,
-                                   int64_t max_q_len, double scale) {
+                                   int64_t max_q_len, double scale,
+                                   const c10::optional<at::Tensor>& k_scale,
+                                   const c10::optional<at::Tensor>& v_scale) {
   // q: [T, Hq, hd] packed rows, token and head dims may be strided (a view
   // of the qkv GEMM output); block_table: [B, max_blocks] int32;
   // cu_q_lens: [B+1] int32 cumulative query counts; seq_lens: [B] int32
   // valid tokens per row including this call's query tokens; max_q_len:
   // host bound on every row's query count (sizes the grid, no device sync).
-  check_page_pools(k_pages, v_pages);
+  const bool fp8 = check_page_pools(k_pages, v_pages, k_scale, v_scale);
   const int64_t num_pages = k_pages.size(0);
   const int Hkv = (int)k_pages.size(1), ps = (int)k_pages.size(2);
   const int hd = (int)k_pages.size(3);
@@ -715,7 +774,8 @@ at::Tensor paged_attention_prefill(const at::Tensor& q,
       block_table.data_ptr(), cu_q_lens.data_ptr(), seq_lens.data_ptr(),
       out.data_ptr(), (long)T, (long)q.stride(0), (long)q.stride(1), (int)B,
       (int)Hq, Hkv, hd, ps, (int)num_pages, (int)max_blocks, (int)max_q_len,
-      (float)scale, cur_stream(q));
+      (float)scale, (int)fp8, scale_ptr(k_scale), scale_ptr(v_scale),
+      cur_stream(q));
   TORCH_CHECK(rc == 0, "paged_attention_prefill: no kernel for head_dim ", hd,
               " group ", G);
   return out;

@@ -32,12 +32,21 @@
 // zero-fills out). All index math on device-side int32 inputs is done in
 // 64 bits. The host passes scale > 0 (the row max is taken before scaling).
 //
+// fp8 pools (template parameter FP8; OCP e4m3 bytes, static fp32 scales per
+// kv head as in paged_attention.hip) differ at staging only: a thread loads
+// 16 B = 16 elements of one key row, keeps the raw bytes in the prefetch
+// registers, and converts to bf16 (exact) when it writes the same Ks / Vs
+// tiles. k_scale folds into the score scale, v_scale into the epilogue's
+// 1/l.
+//
 // No torch headers here; bindings.cpp declares the extern "C" launcher.
 
 #include <hip/hip_runtime.h>
 
 typedef unsigned short u16;
 typedef ushort vec8u __attribute__((ext_vector_type(8)));
+typedef unsigned int vec4w __attribute__((ext_vector_type(4)));
+typedef float vec2f __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -50,17 +59,59 @@ namespace {
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
-template <int HD, int G>
+// One 16 B chunk of a K/V row as it is loaded from the pool and held in the
+// prefetch registers: 8 bf16 or 16 e4m3 bytes. to_lds writes it to the bf16
+// LDS tile at `dst` (16 B aligned).
+template <bool FP8>
+struct Chunk {
+  typedef u16 elem;
+  typedef vec8u vec;
+  static constexpr int N = 8;  // elements
+  static __device__ __forceinline__ void to_lds(u16* dst, vec v) {
+    *reinterpret_cast<vec8u*>(dst) = v;
+  }
+};
+template <>
+struct Chunk<true> {
+  typedef unsigned char elem;
+  typedef vec4w vec;
+  static constexpr int N = 16;
+  // e4m3 -> fp32 has at most 3 mantissa bits, so its high half is the
+  // exact bf16
+  static __device__ __forceinline__ unsigned bf16_pair(vec2f f) {
+    return (__float_as_uint(f[0]) >> 16) |
+           (__float_as_uint(f[1]) & 0xffff0000u);
+  }
+  static __device__ __forceinline__ void to_lds(u16* dst, vec v) {
+    vec4w o[2];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      o[w >> 1][2 * (w & 1)] =
+          bf16_pair(__builtin_amdgcn_cvt_pk_f32_fp8(v[w], false));
+      o[w >> 1][2 * (w & 1) + 1] =
+          bf16_pair(__builtin_amdgcn_cvt_pk_f32_fp8(v[w], true));
+    }
+    *reinterpret_cast<vec4w*>(dst) = o[0];
+    *reinterpret_cast<vec4w*>(dst + 8) = o[1];
+  }
+};
+
+template <int HD, int G, bool FP8>
 __global__ __launch_bounds__(PP_THREADS, 2) void paged_prefill_kernel(
-    const u16* __restrict__ q, const u16* __restrict__ k_pages,
-    const u16* __restrict__ v_pages, const int* __restrict__ block_table,
-    const int* __restrict__ cu_q_lens, const int* __restrict__ seq_lens,
-    u16* __restrict__ out, long T, long q_st, long q_sh, int Hkv,
-    int num_pages, int max_blocks, int page_shift, float qscale) {
+    const u16* __restrict__ q,
+    const typename Chunk<FP8>::elem* __restrict__ k_pages,
+    const typename Chunk<FP8>::elem* __restrict__ v_pages,
+    const int* __restrict__ block_table, const int* __restrict__ cu_q_lens,
+    const int* __restrict__ seq_lens, u16* __restrict__ out, long T,
+    long q_st, long q_sh, int Hkv, int num_pages, int max_blocks,
+    int page_shift, float qscale, const float* __restrict__ k_scale,
+    const float* __restrict__ v_scale) {
+  typedef typename Chunk<FP8>::vec cvec;
+  constexpr int CE = Chunk<FP8>::N;      // elements per 16 B chunk
   constexpr int TQ = PP_MROWS / G;       // query tokens per workgroup
   constexpr int TW = 32 / G;             // query tokens per wave
   constexpr int LDK = HD + 8;            // LDS row stride (elements), 16 B pad
-  constexpr int CPR = HD / 8;            // 16 B chunks per K/V row
+  constexpr int CPR = HD / CE;           // 16 B chunks per K/V row
   constexpr int NLD = PP_KT * CPR / PP_THREADS;  // chunks per thread and tile
   constexpr int KS = HD / 16;            // k-steps of S^T = K Q^T
   constexpr int DB = HD / 32;            // 32-row blocks of O^T
@@ -84,6 +135,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void paged_prefill_kernel(
   if (hi <= 0) return;
   const int n_hi = (int)hi;
   const int ntiles = (n_hi + PP_KT - 1) / PP_KT;
+  if (FP8) qscale *= k_scale[kvh];  // scores come from the raw K bytes
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -136,7 +188,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void paged_prefill_kernel(
 
   // staging registers for one tile; chunk c = tid + u*256 is 16 B number
   // c % CPR of key c / CPR
-  vec8u kreg[NLD], vreg[NLD];
+  cvec kreg[NLD], vreg[NLD];
   bool kvalid = false;  // wave 0: key `lane` of the staged tile was loaded
   auto fetch = [&](int kt) {
 #pragma unroll
@@ -146,15 +198,15 @@ __global__ __launch_bounds__(PP_THREADS, 2) void paged_prefill_kernel(
       const int t = kt * PP_KT + key;
       int pg = -1;
       if (t < n_hi) pg = bt[t >> page_shift];  // t < cap: inside the row
-      kreg[u] = (vec8u)0;
-      vreg[u] = (vec8u)0;
+      kreg[u] = (cvec)0;
+      vreg[u] = (cvec)0;
       if (pg >= 0 && pg < num_pages) {
         const size_t row = (size_t)pg * page_stride +
                            ((size_t)kvh << page_shift) + (t & (page_size - 1));
         kreg[u] =
-            *reinterpret_cast<const vec8u*>(k_pages + row * HD + part * 8);
+            *reinterpret_cast<const cvec*>(k_pages + row * HD + part * CE);
         vreg[u] =
-            *reinterpret_cast<const vec8u*>(v_pages + row * HD + part * 8);
+            *reinterpret_cast<const cvec*>(v_pages + row * HD + part * CE);
       }
     }
     if (wave == 0) {
@@ -172,8 +224,8 @@ __global__ __launch_bounds__(PP_THREADS, 2) void paged_prefill_kernel(
     for (int u = 0; u < NLD; ++u) {
       const int c = tid + u * PP_THREADS;
       const int key = c / CPR, part = c % CPR;
-      *reinterpret_cast<vec8u*>(&Ks[key * LDK + part * 8]) = kreg[u];
-      *reinterpret_cast<vec8u*>(&Vs[key * LDK + part * 8]) = vreg[u];
+      Chunk<FP8>::to_lds(&Ks[key * LDK + part * CE], kreg[u]);
+      Chunk<FP8>::to_lds(&Vs[key * LDK + part * CE], vreg[u]);
     }
     if (wave == 0) {
       const unsigned long long bal = __ballot(kvalid);
@@ -287,7 +339,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void paged_prefill_kernel(
 
   const float lt = l + __shfl_xor(l, 32, 64);
   if (!colok || !(lt > 0.f)) return;  // out is zero-filled by the binding
-  const float inv = 1.f / lt;
+  const float inv = (FP8 ? v_scale[kvh] : 1.f) / lt;
   const size_t Hq = (size_t)Hkv * G;
   u16* op = out + ((size_t)tok * Hq + head) * HD + 4 * h;
   // registers 4g..4g+3 of block d are O[d*32 + 8g + 4h .. +3]: 8 B stores
@@ -303,21 +355,24 @@ __global__ __launch_bounds__(PP_THREADS, 2) void paged_prefill_kernel(
   }
 }
 
-template <int HD, int G>
+template <int HD, int G, bool FP8>
 void launch_prefill(const void* q, const void* k_pages, const void* v_pages,
                     const int* block_table, const int* cu_q_lens,
                     const int* seq_lens, void* out, long T, long q_st,
                     long q_sh, int B, int Hkv, int num_pages, int max_blocks,
                     int page_shift, int max_q_len, float qscale,
+                    const float* k_scale, const float* v_scale,
                     hipStream_t stream) {
+  typedef typename Chunk<FP8>::elem elem;
   constexpr int TQ = PP_MROWS / G;
   const dim3 grid((unsigned)((max_q_len + TQ - 1) / TQ), (unsigned)Hkv,
                   (unsigned)B);
-  hipLaunchKernelGGL((paged_prefill_kernel<HD, G>), grid, dim3(PP_THREADS), 0,
-                     stream, (const u16*)q, (const u16*)k_pages,
-                     (const u16*)v_pages, block_table, cu_q_lens, seq_lens,
-                     (u16*)out, T, q_st, q_sh, Hkv, num_pages, max_blocks,
-                     page_shift, qscale);
+  hipLaunchKernelGGL((paged_prefill_kernel<HD, G, FP8>), grid,
+                     dim3(PP_THREADS), 0, stream, (const u16*)q,
+                     (const elem*)k_pages, (const elem*)v_pages, block_table,
+                     cu_q_lens, seq_lens, (u16*)out, T, q_st, q_sh, Hkv,
+                     num_pages, max_blocks, page_shift, qscale, k_scale,
+                     v_scale);
 }
 
 }  // namespace
@@ -326,26 +381,34 @@ extern "C" {
 
 // Returns 0, or -1 for a configuration with no instantiation (the binding
 // checks the same set first and reports it). q rows may be strided (q_st,
-// q_sh in elements); out is [T, Hq, hd] contiguous and zero-filled.
+// q_sh in elements); out is [T, Hq, hd] contiguous and zero-filled. fp8 != 0:
+// the pools are e4m3 and k_scale / v_scale are [Hkv] fp32 device arrays;
+// otherwise bf16 pools, and the scales are not read.
 int kt_paged_attention_prefill(const void* q, const void* k_pages,
                                const void* v_pages, const void* block_table,
                                const void* cu_q_lens, const void* seq_lens,
                                void* out, long T, long q_st, long q_sh, int B,
                                int Hq, int Hkv, int hd, int page_size,
                                int num_pages, int max_blocks, int max_q_len,
-                               float scale, hipStream_t stream) {
+                               float scale, int fp8, const void* k_scale,
+                               const void* v_scale, hipStream_t stream) {
   const int G = Hq / Hkv;
   int page_shift = 0;
   while ((1 << page_shift) < page_size) ++page_shift;
   const float qscale = scale * 1.4426950408889634f;
-#define KT_PP_CASE(HD_, G_)                                                  \
-  if (hd == HD_ && G == G_) {                                                \
-    launch_prefill<HD_, G_>(q, k_pages, v_pages, (const int*)block_table,    \
-                            (const int*)cu_q_lens, (const int*)seq_lens,     \
-                            out, T, q_st, q_sh, B, Hkv, num_pages,           \
-                            max_blocks, page_shift, max_q_len, qscale,       \
-                            stream);                                         \
-    return 0;                                                                \
+#define KT_PP_LAUNCH(HD_, G_, FP8_)                                         \
+  launch_prefill<HD_, G_, FP8_>(                                            \
+      q, k_pages, v_pages, (const int*)block_table, (const int*)cu_q_lens,  \
+      (const int*)seq_lens, out, T, q_st, q_sh, B, Hkv, num_pages,          \
+      max_blocks, page_shift, max_q_len, qscale, (const float*)k_scale,     \
+      (const float*)v_scale, stream)
+#define KT_PP_CASE(HD_, G_)           \
+  if (hd == HD_ && G == G_) {         \
+    if (fp8)                          \
+      KT_PP_LAUNCH(HD_, G_, true);    \
+    else                              \
+      KT_PP_LAUNCH(HD_, G_, false);   \
+    return 0;                         \
   }
   KT_PP_CASE(64, 1)
   KT_PP_CASE(64, 2)
@@ -356,6 +419,7 @@ int kt_paged_attention_prefill(const void* q, const void* k_pages,
   KT_PP_CASE(128, 4)
   KT_PP_CASE(128, 8)
 #undef KT_PP_CASE
+#undef KT_PP_LAUNCH
   return -1;
 }
 

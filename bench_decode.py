@@ -9,6 +9,8 @@ on one GPU. Usage:
     python bench_decode.py ... --kv paged --prefill paged
     python bench_decode.py ... --kv paged --kv-dtype fp8
     python bench_decode.py ... --kv paged --prefix-cache --shared-prefix 2048
+    python bench_decode.py ... --sampler fused --temperature 0.8 --top-k 50 \
+        --top-p 0.9
 
 --kv slot (default) is the padded slot cache; --kv paged the block-table
 page pools with the fused decode-attention kernel. --num-splits 0 lets the
@@ -19,7 +21,9 @@ scales: random weights, nothing to calibrate on). --shared-prefix N makes the fi
 same for every request and every run; one engine then serves the warm-up
 and the timed runs, so with --prefix-cache the timed run hits the pages the
 warm-up left. ttft_ms is the wall time of the first step() (all prefills
-plus one decode step), device-synchronised.
+plus one decode step), device-synchronised. --sampler fused picks each
+step's tokens with ops.sample_tokens (one call and one host copy per step);
+--top-k and --top-p need it. --temperature applies to either sampler.
 """
 import argparse
 import json
@@ -47,7 +51,7 @@ def build_model(name, dev):
 
 def make_engine(model, batch, prompt, new, kv="slot", page_size=16,
                 num_splits=0, prefill="cache", prefix_cache=False,
-                kv_dtype="bf16"):
+                kv_dtype="bf16", sampler="torch"):
     from kubetorch_amd.models import BatchedGenerator
 
     kw = {}
@@ -57,20 +61,24 @@ def make_engine(model, batch, prompt, new, kv="slot", page_size=16,
         kw.update(prefill=prefill, prefix_cache=prefix_cache)
     if kv_dtype == "fp8":
         kw.update(kv_dtype="fp8")
+    if sampler != "torch":
+        kw.update(sampler=sampler)
     return BatchedGenerator(model, max_batch=batch, max_len=prompt + new + 8,
                             **kw)
 
 
 def run_once(dev, model, cfg, batch, prompt, new, eng=None, shared=None,
-             **mode):
+             sampling=None, **mode):
     """One full engine run: (generated tokens, seconds of the first step).
-    `shared`: the prompt tokens every request starts with."""
+    `shared`: the prompt tokens every request starts with; `sampling`:
+    submit()'s temperature / top_k / top_p, if any."""
     if eng is None:
         eng = make_engine(model, batch, prompt, new, **mode)
     shared = shared or []
     for i in range(batch):
         p = torch.randint(0, cfg.vocab_size, (prompt - len(shared),))
-        eng.submit(shared + p.tolist(), max_new_tokens=new)
+        eng.submit(shared + p.tolist(), max_new_tokens=new,
+                   **(sampling or {}))
     if dev.type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -115,7 +123,16 @@ def main():
     ap.add_argument("--shared-prefix", type=int, default=0,
                     help="first N prompt tokens equal across requests and "
                          "runs; one engine serves all runs")
+    ap.add_argument("--sampler", default="torch", choices=["torch", "fused"],
+                    help="fused: one ops.sample_tokens call per step")
+    ap.add_argument("--temperature", type=float, default=0.0)
+    ap.add_argument("--top-k", type=int, default=0,
+                    help="needs --sampler fused")
+    ap.add_argument("--top-p", type=float, default=1.0,
+                    help="needs --sampler fused")
     args = ap.parse_args()
+    if args.sampler != "fused" and (args.top_k != 0 or args.top_p != 1.0):
+        ap.error("--top-k and --top-p need --sampler fused")
     if not 0 <= args.shared_prefix <= args.prompt:
         ap.error("--shared-prefix must be in [0, --prompt]")
     if args.kv_dtype == "fp8" and args.kv != "paged":
@@ -131,6 +148,13 @@ def main():
     if args.kv_dtype == "fp8":
         mode.update(kv_dtype="fp8")
     extra = {}
+    if args.sampler != "torch":
+        mode.update(sampler=args.sampler)
+    if args.temperature != 0.0:
+        extra["sampling"] = dict(temperature=args.temperature)
+    if args.top_k != 0 or args.top_p != 1.0:
+        extra.setdefault("sampling", {}).update(top_k=args.top_k,
+                                                top_p=args.top_p)
     eng = None
     if args.shared_prefix:
         gen = torch.Generator().manual_seed(1)
@@ -153,6 +177,9 @@ def main():
             more["hit_tokens"] = eng.prefix_stats["hit_tokens"] - hit0
     if args.kv_dtype == "fp8":
         more["kv_dtype"] = "fp8"
+    if args.sampler != "torch" or "sampling" in extra:
+        more.update(sampler=args.sampler, temperature=args.temperature,
+                    top_k=args.top_k, top_p=args.top_p)
     print(json.dumps({
         "metric": "decode_tokens_per_sec",
         "value": round(new_toks / dt, 2),

@@ -34,10 +34,14 @@ class Generator:
                                   temperature=temperature)
         return out[0].tolist()
 
-    def generate_batch(self, prompts, max_new_tokens=16, kv_dtype=None):
+    def generate_batch(self, prompts, max_new_tokens=16, kv_dtype=None,
+                       sampling=None):
         """Continuous batching over the paged KV cache. kv_dtype="fp8"
         keeps the pages as e4m3 bytes (half the KV memory and decode
-        reads), with scales calibrated on the first prompt."""
+        reads), with scales calibrated on the first prompt. `sampling`:
+        per-prompt dicts of submit()'s temperature / top_k / top_p / seed,
+        drawn by the fused sampler; a seeded request repeats its tokens
+        whatever it is batched with."""
         from kubetorch_amd.models import BatchedGenerator, calibrate_kv_scales
 
         scales = None
@@ -45,8 +49,11 @@ class Generator:
             scales = calibrate_kv_scales(self.model, prompts[0], margin=1.5)
         eng = BatchedGenerator(self.model, max_batch=4, max_len=128,
                                kv="paged", kv_dtype=kv_dtype,
-                               kv_scales=scales)
-        rids = [eng.submit(p, max_new_tokens=max_new_tokens) for p in prompts]
+                               kv_scales=scales,
+                               sampler="fused" if sampling else "torch")
+        sampling = sampling or [{}] * len(prompts)
+        rids = [eng.submit(p, max_new_tokens=max_new_tokens, **s)
+                for p, s in zip(prompts, sampling)]
         out = eng.run()
         return [out[r] for r in rids]
 
@@ -59,5 +66,10 @@ if __name__ == "__main__":
         outs = gen.generate_batch([[1, 2, 3, 4], [9, 8, 7]], max_new_tokens=8,
                                   kv_dtype="fp8")
         print("generated (paged fp8 KV):", outs)
+        outs = gen.generate_batch(
+            [[1, 2, 3, 4], [9, 8, 7]], max_new_tokens=8,
+            sampling=[dict(temperature=0.8, top_k=50, top_p=0.9, seed=1234),
+                      dict()])  # the second request stays greedy
+        print("generated (sampled, seed 1234 / greedy):", outs)
     finally:
         gen.teardown()

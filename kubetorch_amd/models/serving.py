@@ -37,6 +37,13 @@ models/paged_kv.py): every place that touches pages passes the layer's
 scales to the paged ops, which quantise on write and dequantise on read.
 Half the KV bytes per token; the allocator and the prefix cache are the
 same.
+
+`sampler="fused"` (opt-in) picks every step's tokens with one
+ops.sample_tokens call over all rows (per-request temperature, top_k, top_p
+and seed; a counter-based draw, so a request's tokens do not depend on its
+batch mates) and one copy of the token ids to the host, in place of one
+host-side `_sample` and sync per request. Under a graph the call is part of
+the captured step. The default, sampler="torch", is `_sample` as it was.
 """
 from dataclasses import dataclass, field
 
@@ -55,13 +62,22 @@ class _Request:
     out: list = field(default_factory=list)
     slot: int = -1
     cached_tokens: int = 0        # prompt tokens served from shared pages
+    top_k: int = 0                # sampler="fused" only, as is what follows
+    top_p: float = 1.0
+    seed: int = 0
 
 
 class BatchedGenerator:
     def __init__(self, model, max_batch=8, max_len=None, device=None,
                  prefill_chunk=None, graph=None, kv="slot", page_size=16,
                  num_pages=None, num_splits=None, prefill="cache",
-                 prefix_cache=False, kv_dtype=None, kv_scales=None):
+                 prefix_cache=False, kv_dtype=None, kv_scales=None,
+                 sampler="torch", sampler_seed=0):
+        if sampler not in ("torch", "fused"):
+            raise ValueError(
+                f"sampler must be 'torch' or 'fused', got {sampler!r}")
+        self._fused = sampler == "fused"
+        self._sampler_seed = int(sampler_seed)
         if kv not in ("slot", "paged"):
             raise ValueError(f"kv must be 'slot' or 'paged', got {kv!r}")
         if kv_dtype not in (None, "fp8"):
@@ -149,12 +165,33 @@ class BatchedGenerator:
         # host mirror of per-slot lengths: picks the smallest captured
         # horizon bucket without a device sync
         self._host_lens = [0] * max_batch
+        # sampler="fused": per-slot sampling parameters of the graph path
+        # (static buffers, rewritten when a slot's occupant changes) and
+        # the eager path's parameter rows, kept while the active set stays
+        self._g_samp = None
+        self._g_owner = [None] * max_batch
+        self._e_samp = (None, None)
 
     # -- client API ----------------------------------------------------------
     def submit(self, prompt_ids, max_new_tokens=32, temperature=0.0,
-               stop_token=None):
+               stop_token=None, top_k=0, top_p=1.0, seed=None):
+        """Queue a request; returns its id. top_k, top_p and seed need
+        sampler="fused" (ops.sample_tokens has their meaning): top_k=0 and
+        top_p=1.0 are off, seed=None is (sampler_seed << 32) | rid, so a
+        fresh engine given the same submissions repeats its outputs. A
+        request's tokens depend on its seed, never on its batch mates."""
+        if not self._fused:
+            if top_k != 0 or top_p != 1.0 or seed is not None:
+                raise ValueError(
+                    "top_k, top_p and seed need sampler='fused'")
+        elif not (temperature >= 0 and top_k >= 0 and 0 < top_p <= 1):
+            raise ValueError("need temperature >= 0, top_k >= 0 and "
+                             "0 < top_p <= 1")
         rid = self._next_rid
         self._next_rid += 1
+        if seed is None:
+            seed = (self._sampler_seed << 32) | rid
+        seed = (int(seed) + 2 ** 63) % 2 ** 64 - 2 ** 63   # as int64
         prompt = torch.as_tensor(prompt_ids, dtype=torch.long,
                                  device=self.device).reshape(-1)
         if prompt.numel() + max_new_tokens > self.max_len:
@@ -163,7 +200,9 @@ class BatchedGenerator:
                 prompt.numel() + max_new_tokens) > self._pkv.num_pages:
             raise ValueError("request needs more pages than the pool holds")
         self.pending.append(_Request(rid, prompt, max_new_tokens,
-                                     temperature, stop_token))
+                                     temperature, stop_token,
+                                     top_k=int(top_k), top_p=float(top_p),
+                                     seed=seed))
         return rid
 
     @property
@@ -244,12 +283,16 @@ class BatchedGenerator:
         for s0 in range(0, S0, chunk):
             logits = self.model._forward_cached(batch[:, s0:s0 + chunk],
                                                 cache)
+        toks = self._sample_rows(group, logits) if self._fused else None
         for j, req in enumerate(group):
             self._store_prefill(req, cache, j, S0)
             self.lens[req.slot] = S0
             self._host_lens[req.slot] = S0
             req.out = req.prompt.tolist()
-            self._emit(req, logits[j])
+            if toks is None:
+                self._emit(req, logits[j])
+            else:
+                self._emit_token(req, toks[j])
 
     def _store_prefill(self, req, cache, j, S0):
         """Move row j of a prefill cache into the request's slot (slot
@@ -303,6 +346,15 @@ class BatchedGenerator:
                 max(b - a for a, b in zip(cu, cu[1:])),
                 torch.tensor(last).to(dev))
             rest = []
+            toks = {}
+            if self._fused:  # one call for the rows whose prompt is in
+                fin = [j for j, r in enumerate(todo)
+                       if done[r.rid] >= r.prompt.numel()]
+                if fin:
+                    rows = logits if len(fin) == len(todo) else \
+                        logits[torch.tensor(fin).to(dev)]
+                    toks = dict(zip(fin, self._sample_rows(
+                        [todo[j] for j in fin], rows)))
             for j, r in enumerate(todo):
                 S0 = r.prompt.numel()
                 if done[r.rid] < S0:
@@ -313,7 +365,10 @@ class BatchedGenerator:
                 r.out = r.prompt.tolist()
                 if self._prefix:  # before _emit, which may release the slot
                     self._pkv.publish(r.slot, r.out)
-                self._emit(r, logits[j])
+                if self._fused:
+                    self._emit_token(r, toks[j])
+                else:
+                    self._emit(r, logits[j])
             todo = rest
 
     def _prefill_math(self, toks, pos, slot_map, table, cu, seq_lens, max_q,
@@ -348,8 +403,35 @@ class BatchedGenerator:
             return int(torch.multinomial(probs, 1))
         return int(logits.argmax(-1))
 
+    # -- sampler="fused": ops.sample_tokens over all rows of a step ----------
+    @staticmethod
+    def _generated(req):
+        """Tokens the request has generated so far = its next draw's
+        offset (0 for the token that comes out of prefill)."""
+        return max(0, len(req.out) - req.prompt.numel())
+
+    def _sample_params(self, reqs):
+        """The five [len(reqs)] parameter vectors of ops.sample_tokens on
+        the device; None entries (free graph slots) are greedy rows."""
+        rows = [(r.temperature, r.top_k, r.top_p, r.seed, self._generated(r))
+                if r is not None else (0.0, 0, 1.0, 0, 0) for r in reqs]
+        t, k, p, sd, off = zip(*rows)
+        dev = self.device
+        return [torch.tensor(t, dtype=torch.float32).to(dev),
+                torch.tensor(k, dtype=torch.int32).to(dev),
+                torch.tensor(p, dtype=torch.float32).to(dev),
+                torch.tensor(sd, dtype=torch.int64).to(dev),
+                torch.tensor(off, dtype=torch.int64).to(dev)]
+
+    def _sample_rows(self, reqs, logits):
+        """Row j of logits [len(reqs), vocab] is request j's: one sampler
+        call and one copy to the host -> list of token ids."""
+        return ops.sample_tokens(logits, *self._sample_params(reqs)).tolist()
+
     def _emit(self, req, logits):
-        nxt = self._sample(req, logits)
+        self._emit_token(req, self._sample(req, logits))
+
+    def _emit_token(self, req, nxt):
         req.out.append(nxt)
         req.next_tok = nxt
         done = (len(req.out) - req.prompt.numel() >= req.max_new_tokens
@@ -447,6 +529,12 @@ class BatchedGenerator:
         else:
             logits = self._slot_math(self._g_toks, self.lens, L)
         self.lens.add_(self._g_act)  # active slots advance one position
+        if self._fused:
+            # the step's tokens [max_batch] instead of its logits; free
+            # slots are greedy rows over garbage and are ignored
+            toks = ops.sample_tokens(logits, *self._g_samp)
+            self._g_samp[4].add_(self._g_act)  # offset: one more drawn
+            return toks
         return logits
 
     def _bucket_for(self, need):
@@ -468,11 +556,16 @@ class BatchedGenerator:
             self._g_act = torch.zeros(self.max_batch, dtype=torch.long,
                                       device=self.device)
             self._g_pool = torch.cuda.graph_pool_handle()
+            if self._fused:
+                self._g_samp = self._sample_params([None] * self.max_batch)
         lens_snapshot = self.lens.clone()
+        off_snapshot = self._g_samp[4].clone() if self._fused else None
         horizon = None if self._paged else L
         for _ in range(2):  # warm up allocator/workspaces pre-capture
             self._decode_math(horizon)
         self.lens.copy_(lens_snapshot)
+        if self._fused:
+            self._g_samp[4].copy_(off_snapshot)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, pool=self._g_pool):
@@ -498,6 +591,18 @@ class BatchedGenerator:
                            non_blocking=True)
         self._g_act.copy_(torch.tensor(act, dtype=torch.long),
                           non_blocking=True)
+        if self._fused:
+            owner = [r.rid if r is not None else None for r in self.slots]
+            if owner != self._g_owner:  # a slot's occupant changed
+                for buf, new in zip(self._g_samp,
+                                    self._sample_params(self.slots)):
+                    buf.copy_(new, non_blocking=True)
+                self._g_owner = owner
+            graph.replay()
+            toks = logits.tolist()  # the graph's output is the tokens
+            for s in active:
+                self._emit_token(self.slots[s], toks[s])
+            return
         graph.replay()
         for s in active:
             self._emit(self.slots[s], logits[s])
@@ -516,6 +621,19 @@ class BatchedGenerator:
             logits = self._slot_math(toks, lens, int(lens.max().item()) + 1,
                                      idx)
         self.lens[idx] += 1
+        if self._fused:
+            # the parameter rows stay on the device while the same requests
+            # are active; only their offsets move, one draw per step
+            rids = [self.slots[s].rid for s in active]
+            if self._e_samp[0] != rids:
+                self._e_samp = (rids, self._sample_params(
+                    [self.slots[s] for s in active]))
+            params = self._e_samp[1]
+            toks = ops.sample_tokens(logits, *params).tolist()
+            params[4] += 1
+            for j, s in enumerate(active):
+                self._emit_token(self.slots[s], toks[j])
+            return
         for j, s in enumerate(active):
             self._emit(self.slots[s], logits[j])
 

@@ -930,6 +930,170 @@ def paged_attention_prefill(q, k_pages, v_pages, block_table, cu_q_lens,
 
 
 # ---------------------------------------------------------------------------
+# Batched token sampling (serving decode): temperature, top-k, top-p and a
+# seeded draw per row. Inference-only, no autograd, no host sync.
+# ---------------------------------------------------------------------------
+SAMPLER_MAX_VOCAB = 262144
+_M32 = 0xFFFFFFFF
+
+
+def _mulhilo32(m, c):
+    """(high, low) 32-bit words of m * c for a constant m < 2^32 and an
+    int64 tensor c of values < 2^32, without leaving int64: c goes in as
+    two 16-bit halves."""
+    a = m * (c >> 16)          # < 2^48
+    b = m * (c & 0xFFFF)       # < 2^48
+    t = ((a & 0xFFFF) << 16) + b
+    return (a >> 16) + (t >> 32), t & _M32
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on int64 tensors of 32-bit words: counter [..., 4],
+    key [..., 2] -> [..., 4]. Matches the Random123 known answers."""
+    c0, c1, c2, c3 = (counter[..., i] for i in range(4))
+    k0, k1 = key[..., 0], key[..., 1]
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(0xD2511F53, c0)
+        hi1, lo1 = _mulhilo32(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0 = (k0 + 0x9E3779B9) & _M32
+        k1 = (k1 + 0xBB67AE85) & _M32
+    return torch.stack([c0, c1, c2, c3], dim=-1)
+
+
+def _sample_bits(seed, offset, V):
+    """r [B, V] int64: the 23 random bits of every token. Token i uses word
+    i & 3 of the Philox block with key (seed lo, seed hi) and counter
+    (i >> 2, offset lo, offset hi, 0); int64 seeds and offsets are read as
+    two's complement."""
+    B = seed.shape[0]
+    nblk = (V + 3) // 4
+    blk = torch.arange(nblk, device=seed.device).view(1, nblk).expand(B, nblk)
+    lo = lambda t: (t & _M32).view(B, 1).expand(B, nblk)
+    hi = lambda t: ((t >> 32) & _M32).view(B, 1).expand(B, nblk)
+    counter = torch.stack([blk, lo(offset), hi(offset),
+                           torch.zeros_like(blk)], dim=-1)
+    key = torch.stack([lo(seed), hi(seed)], dim=-1)
+    words = philox4x32_10(counter, key)            # [B, nblk, 4]
+    return words.reshape(B, nblk * 4)[:, :V] >> 9
+
+
+def _sample_tokens_ref(logits, temperature, top_k, top_p, seed, offset,
+                       details=False):
+    """The float64 composition that defines sample_tokens (see there); pure
+    tensor ops on the logits' device, no host read. details=True also
+    returns (kept [B, V] bool, score [B, V] float64) of the sampled rows:
+    rows that are greedy, hold a +inf or nothing above -inf are decided by
+    arg-max alone and have kept all False."""
+    B, V = logits.shape
+    x = logits.double()
+    ninf = float("-inf")
+    x = torch.where(x.isnan(), torch.full_like(x, ninf), x)
+    T = temperature.double().view(B, 1)
+    xmax = x.max(dim=1, keepdim=True).values
+    first_max = (x == xmax).to(torch.uint8).argmax(dim=1)
+    sampled = (T > 0) & (xmax > ninf) & (xmax < float("inf"))
+    Ts = torch.where(sampled, T, torch.ones_like(T))
+    # top-k: keep what is >= the k-th largest value (ties all stay)
+    k = top_k.long().view(B, 1)
+    xs, order = x.sort(dim=1, descending=True, stable=True)
+    kth = xs.gather(1, (k - 1).clamp(0, V - 1))
+    kept = torch.where((k > 0) & (k < V), x >= kth, torch.ones_like(x) > 0)
+    # weights of the kept tokens; top-p on the mass strictly above a token
+    d = torch.where(sampled, x - xmax, torch.zeros_like(x))
+    w = torch.where(kept, torch.exp(d / Ts), torch.zeros_like(x))
+    Z = w.sum(dim=1, keepdim=True)
+    ws = w.gather(1, order)
+    before = ws.cumsum(dim=1) - ws                 # mass ahead in sort order
+    run_start = torch.ones_like(xs, dtype=torch.bool)
+    run_start[:, 1:] = xs[:, 1:] != xs[:, :-1]
+    above_s = torch.where(run_start, before,
+                          torch.zeros_like(before)).cummax(dim=1).values
+    above = torch.empty_like(above_s).scatter_(1, order, above_s)
+    p = top_p.double().view(B, 1)
+    stays = (above < p * Z) | (x == xmax)
+    kept = kept & torch.where(p < 1, stays, torch.ones_like(stays))
+    # exponential race among the kept tokens
+    r = _sample_bits(seed, offset, V)
+    v = (r.double() + 0.5) * 2.0 ** -23
+    E = -torch.log1p(-v)
+    score = torch.where(sampled, x, torch.zeros_like(x)) / Ts - torch.log(E)
+    score = torch.where(kept, score, torch.full_like(score, ninf))
+    smax = score.max(dim=1, keepdim=True).values
+    drawn = (score == smax).to(torch.uint8).argmax(dim=1)
+    token = torch.where(sampled.view(B), drawn, first_max)
+    token = torch.where(xmax.view(B) > ninf, token, torch.zeros_like(token))
+    if details:
+        kept = kept & sampled
+        return token, kept, torch.where(kept, score,
+                                        torch.full_like(score, ninf))
+    return token
+
+
+def _sampler_kernel_ok(logits):
+    """What the kernel takes; everything else runs the reference."""
+    B, V = logits.shape
+    return (logits.is_cuda and logits.dtype == torch.bfloat16
+            and 1 <= V <= SAMPLER_MAX_VOCAB
+            and (V == 1 or logits.stride(1) == 1)
+            and logits.data_ptr() % 16 == 0
+            and (B <= 1 or (logits.stride(0) >= 0
+                            and logits.stride(0) % 8 == 0)))
+
+
+def sample_tokens(logits, temperature, top_k, top_p, seed, offset):
+    """One token per row of logits [B, V] -> int64 [B], each row with its
+    own temperature [B] fp32, top_k [B] int32, top_p [B] fp32, seed [B]
+    int64 and offset [B] int64, all on the logits' device: nothing is read
+    on the host, the call makes no sync and can be captured in a graph.
+
+    Per row, from the logits as given:
+      1. NaN counts as -inf; a row with nothing above -inf returns 0. The
+         result is always in [0, V).
+      2. temperature == 0 (or anything not > 0) is greedy: the lowest index
+         of the maximum; the other parameters are ignored. A row that holds
+         +inf is decided the same way.
+      3. 0 < top_k < V keeps the logits >= the k-th largest value (ties at
+         the boundary all stay); top_k == 0 is off.
+      4. w_i = exp((x_i - max) / T) over the kept logits, Z = sum(w).
+      5. top_p < 1 keeps token i iff sum(w_j : x_j > x_i) < top_p * Z; the
+         maximum always stays, equal logits stay or go together.
+      6. The draw is an exponential race with noise that depends only on
+         (seed, offset, i): Philox4x32-10, key (seed lo, seed hi), counter
+         (i >> 2, offset lo, offset hi, 0), token i uses word i & 3;
+         r = word >> 9, v = (r + 0.5) * 2^-23, E = -log1p(-v),
+         score_i = x_i / T - log(E). The result is the lowest index of the
+         maximum score among the kept tokens.
+    A row's result depends on nothing but the row and its parameters.
+
+    bf16 GPU logits with V <= 262144 and 16-byte aligned rows run the HIP
+    kernel (fp32 scores, bit-identical run to run); the CPU and every other
+    input run the same rules as a float64 torch composition, which is the
+    reference. Arguments are checked by shape, dtype and device only."""
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError("logits must be [B, V] with V >= 1")
+    if not logits.is_floating_point():
+        raise ValueError("logits must be a floating-point tensor")
+    _no_grad_inputs("sample_tokens", logits)
+    B = logits.shape[0]
+    for name, t, dt in (("temperature", temperature, torch.float32),
+                        ("top_k", top_k, torch.int32),
+                        ("top_p", top_p, torch.float32),
+                        ("seed", seed, torch.int64),
+                        ("offset", offset, torch.int64)):
+        if not torch.is_tensor(t) or t.dtype != dt \
+                or tuple(t.shape) != (B,) or t.device != logits.device:
+            raise ValueError(f"{name} must be [B] {dt} on the logits' device")
+    if B == 0:
+        return torch.empty(0, dtype=torch.long, device=logits.device)
+    if _sampler_kernel_ok(logits):
+        return _ext().sample_tokens(logits, temperature.contiguous(),
+                                    top_k.contiguous(), top_p.contiguous(),
+                                    seed.contiguous(), offset.contiguous())
+    return _sample_tokens_ref(logits, temperature, top_k, top_p, seed, offset)
+
+
+# ---------------------------------------------------------------------------
 # Multi-tensor pack/unpack (GPU data plane: packed state-dict transfers)
 # ---------------------------------------------------------------------------
 PACK_ALIGN = 16  # bytes; segment starts in the flat buffer are 16B-aligned

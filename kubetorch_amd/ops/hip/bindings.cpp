@@ -91,6 +91,10 @@ int kt_paged_attention_prefill(const void* q, const void* k_pages,
                                int num_pages, int max_blocks, int max_q_len,
                                float scale, int fp8, const void* k_scale,
                                const void* v_scale, hipStream_t stream);
+void kt_sample_tokens(const void* logits, long row_stride, int B, int V,
+                      const void* temperature, const void* top_k,
+                      const void* top_p, const void* seed, const void* offset,
+                      void* out, hipStream_t stream);
 }
 
 namespace {
@@ -781,6 +785,51 @@ at::Tensor paged_attention_prefill(const at::Tensor& q,
   return out;
 }
 
+at::Tensor sample_tokens(const at::Tensor& logits,
+                         const at::Tensor& temperature,
+                         const at::Tensor& top_k, const at::Tensor& top_p,
+                         const at::Tensor& seed, const at::Tensor& offset) {
+  // logits: [B, V] bf16, last dim contiguous, row base and stride 16 B
+  // aligned (ops.sample_tokens sends everything else to the reference).
+  // The five parameter vectors are [B] on the logits' device; their values
+  // are not looked at here (that would be a device sync).
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16 &&
+                  logits.dim() == 2,
+              "logits must be [B, V] bf16 on GPU");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= 262144, "V must be in [1, 262144], got ", V);
+  TORCH_CHECK(B < (int64_t)INT32_MAX, "batch too large");
+  TORCH_CHECK(V == 1 || logits.stride(1) == 1,
+              "logits' last dim must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0 &&
+                  (B <= 1 ||
+                   (logits.stride(0) >= 0 && logits.stride(0) % 8 == 0)),
+              "logits rows must be 16-byte aligned");
+  const struct {
+    const at::Tensor* t;
+    at::ScalarType dt;
+    const char* name;
+  } params[] = {{&temperature, at::kFloat, "temperature must be [B] fp32"},
+                {&top_k, at::kInt, "top_k must be [B] int32"},
+                {&top_p, at::kFloat, "top_p must be [B] fp32"},
+                {&seed, at::kLong, "seed must be [B] int64"},
+                {&offset, at::kLong, "offset must be [B] int64"}};
+  for (const auto& p : params) {
+    TORCH_CHECK(p.t->is_cuda() && p.t->device() == logits.device() &&
+                    p.t->scalar_type() == p.dt && p.t->dim() == 1 &&
+                    p.t->size(0) == B && p.t->is_contiguous(),
+                p.name, ", contiguous, on the logits' device");
+  }
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
+  auto out = at::empty({B}, logits.options().dtype(at::kLong));
+  if (B == 0) return out;
+  kt_sample_tokens(logits.data_ptr(), B > 1 ? (long)logits.stride(0) : 0,
+                   (int)B, (int)V, temperature.data_ptr(), top_k.data_ptr(),
+                   top_p.data_ptr(), seed.data_ptr(), offset.data_ptr(),
+                   out.data_ptr(), cur_stream(logits));
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -826,4 +875,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "Single-token GQA attention over a block-table paged KV cache");
   mod.def("paged_attention_prefill", &paged_attention_prefill,
           "Causal GQA attention of packed query tokens over a paged KV cache");
+  mod.def("sample_tokens", &sample_tokens,
+          "Per-row temperature / top-k / top-p / seeded token sampling");
 }

@@ -398,6 +398,8 @@ def flash_attention(q, k, v, scale=None, impl="ck"):
     REQUIRES q pre-scaled by scale*log2e (fold it into ops.rope's oscale);
     impl="wmma" runs the in-tree rocWMMA kernel (ops/hip/attention.hip,
     requires S % 128 == 0)."""
+    if impl not in ("ck", "v3", "wmma"):
+        raise ValueError(f'impl must be "ck", "v3" or "wmma", got {impl!r}')
     if scale is None:
         scale = q.shape[-1] ** -0.5
     return _FlashAttention.apply(q, k, v, scale, impl)

@@ -335,17 +335,69 @@ void adamw_(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v,
            bc2, (float)grad_scale, cur_stream(p));
 }
 
+// Host checks shared by the dense attention bindings. The kernels trust
+// their arguments, so every check runs before the first allocation and
+// launch: a call that fails here has written nothing.
+void check_attn_tensor(const char* fn, const char* name, const at::Tensor& t,
+                       const at::Tensor& q) {
+  TORCH_CHECK(t.is_cuda(), fn, ": ", name, " must be on GPU");
+  TORCH_CHECK(t.device() == q.device(), fn, ": ", name,
+              " must be on the same device as q");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, fn, ": ", name,
+              " must be bf16");
+  TORCH_CHECK(t.dim() == 4 && t.size(3) == 128, fn, ": ", name,
+              " must be [B,H,S,128]");
+  TORCH_CHECK(t.stride(3) == 1, fn, ": ", name,
+              " last dim must be contiguous");
+}
+
+struct AttnDims {
+  int B, Hq, Hkv, S;
+};
+
+// q [B,Hq,S,128], k/v [B,Hkv,S,128]; S must be a multiple of `s_tile`
+// (the kernel's query tile: no padded instantiation is validated).
+AttnDims check_attn_qkv(const char* fn, const at::Tensor& q,
+                        const at::Tensor& k, const at::Tensor& v,
+                        int s_tile) {
+  check_attn_tensor(fn, "q", q, q);
+  check_attn_tensor(fn, "k", k, q);
+  check_attn_tensor(fn, "v", v, q);
+  TORCH_CHECK(k.sizes() == v.sizes(), fn, ": k and v shapes differ");
+  TORCH_CHECK(q.size(0) >= 1 && q.size(1) >= 1 && q.size(2) >= 1, fn,
+              ": B, Hq and S must be >= 1");
+  TORCH_CHECK(k.size(0) == q.size(0), fn, ": k batch ", k.size(0),
+              " != q batch ", q.size(0));
+  TORCH_CHECK(k.size(2) == q.size(2), fn, ": k sequence length ", k.size(2),
+              " != q sequence length ", q.size(2));
+  TORCH_CHECK(k.size(1) >= 1 && q.size(1) % k.size(1) == 0, fn,
+              ": GQA requires Hkv >= 1 and Hq % Hkv == 0");
+  TORCH_CHECK(q.size(2) % s_tile == 0, fn, ": S must be a multiple of ",
+              s_tile, ", got ", q.size(2));
+  return {(int)q.size(0), (int)q.size(1), (int)k.size(1), (int)q.size(2)};
+}
+
+// The CK kernels take element strides as 32-bit ck_tile::index_t. This
+// bounds each stride on its own and nothing more: not the products the
+// kernels form inside a tile window (stride(2) * (S - 1)), not the
+// launcher's own (index_t)Hq * S for the lse batch stride, and not overlap:
+// a q expanded over batch or heads (stride 0) passes, and o, allocated with
+// q's strides, then aliases itself.
+void check_attn_strides(const char* fn, const char* name,
+                        const at::Tensor& t) {
+  for (int d = 0; d < 3; ++d)
+    TORCH_CHECK(t.stride(d) >= 0 && t.stride(d) < (1LL << 31), fn, ": ", name,
+                " stride(", d, ") = ", t.stride(d),
+                " does not fit the kernel's 32-bit index");
+}
+
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k,
                                  const at::Tensor& v, double scale) {
   // q: [B, Hq, S, 128]; k/v: [B, Hkv, S, 128]; causal, bf16.
-  CHECK_BF16_CONTIG(q);
-  CHECK_BF16_CONTIG(k);
-  CHECK_BF16_CONTIG(v);
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == 128, "q must be [B,H,S,128]");
-  const int B = (int)q.size(0), Hq = (int)q.size(1), S = (int)q.size(2);
-  const int Hkv = (int)k.size(1);
-  TORCH_CHECK(S % 128 == 0 && S >= 256, "S must be a multiple of 128, >= 256");
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  const auto [B, Hq, Hkv, S] = check_attn_qkv("attn_fwd", q, k, v, 128);
+  TORCH_CHECK(S >= 256, "attn_fwd: S must be a multiple of 128, >= 256");
+  TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous(),
+              "attn_fwd: q, k and v must be contiguous");
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
   auto o = at::empty_like(q);
   auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
@@ -361,18 +413,12 @@ std::vector<at::Tensor> attn_fwd_ck_impl(const at::Tensor& q,
   // CK-tile FMHA fwd: q [B,Hq,S,128], k/v [B,Hkv,S,128], causal, LSE out.
   // Strided inputs are supported (last dim must be contiguous) — [B,S,H,D]
   // permuted views go straight in, no transpose copies.
-#define CHECK_BF16_LASTC(t)                                             \
-  TORCH_CHECK((t).is_cuda(), #t " must be on GPU");                     \
-  TORCH_CHECK((t).scalar_type() == at::kBFloat16, #t " must be bf16");  \
-  TORCH_CHECK((t).stride(3) == 1, #t " last dim must be contiguous")
-  CHECK_BF16_LASTC(q);
-  CHECK_BF16_LASTC(k);
-  CHECK_BF16_LASTC(v);
-#undef CHECK_BF16_LASTC
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == 128, "q must be [B,H,S,128]");
-  const int B = (int)q.size(0), Hq = (int)q.size(1), S = (int)q.size(2);
-  const int Hkv = (int)k.size(1);
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  // S % 128: the kernels' M0 tile; the padded tail path is not validated.
+  const char* name = trload ? "attn_fwd_ck_tr" : "attn_fwd_ck";
+  const auto [B, Hq, Hkv, S] = check_attn_qkv(name, q, k, v, 128);
+  check_attn_strides(name, "q", q);  // o takes q's strides
+  check_attn_strides(name, "k", k);
+  check_attn_strides(name, "v", v);
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
   // write O in the same (possibly permuted) layout as q
   auto o = at::empty_strided(q.sizes(), q.strides(), q.options());
@@ -404,12 +450,11 @@ std::vector<at::Tensor> attn_fwd_v3(const at::Tensor& q, const at::Tensor& k,
                                     const at::Tensor& v, double scale,
                                     bool prescaled) {
   // AITER-schedule v3 kernel (8 warps, M0=256) with LSE output.
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == 128 && q.stride(3) == 1);
-  TORCH_CHECK(k.stride(3) == 1 && v.stride(3) == 1);
-  const int B = (int)q.size(0), Hq = (int)q.size(1), S = (int)q.size(2);
-  const int Hkv = (int)k.size(1);
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  // S % 256: its M0 tile.
+  const auto [B, Hq, Hkv, S] = check_attn_qkv("attn_fwd_v3", q, k, v, 256);
+  check_attn_strides("attn_fwd_v3", "q", q);  // o takes q's strides
+  check_attn_strides("attn_fwd_v3", "k", k);
+  check_attn_strides("attn_fwd_v3", "v", v);
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
   // LSE-correct scaling contract: the v3 pipeline tracks the rowmax `m` of
   // the RAW gemm0 scores and its LSE epilogue computes m/log2e + log(l),
@@ -441,15 +486,22 @@ std::vector<at::Tensor> attn_bwd_ck(const at::Tensor& grad_out,
   // CK-tile GQA-native FMHA backward (attention_ck_bwd.hip). Contiguous
   // [B,H,S,128] bf16 in; returns (dq, dk, dv) with dk/dv Hq-EXPANDED — the
   // autograd wrapper sums KV-head groups.
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(q.dim() == 4 && q.size(3) == 128);
-  TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous());
-  TORCH_CHECK(o.is_contiguous() && lse.is_contiguous());
-  const int B = (int)q.size(0), Hq = (int)q.size(1), S = (int)q.size(2);
-  const int Hkv = (int)k.size(1);
-  TORCH_CHECK(Hq % Hkv == 0 && S % 128 == 0);
-  TORCH_CHECK(lse.sizes() == at::IntArrayRef({B, Hq, S}) &&
-              lse.scalar_type() == at::kFloat);
+  // S % 128: the N0 key block of pipes 0-2 and a multiple of every tile.
+  const auto [B, Hq, Hkv, S] = check_attn_qkv("attn_bwd_ck", q, k, v, 128);
+  check_attn_tensor("attn_bwd_ck", "grad_out", grad_out, q);
+  check_attn_tensor("attn_bwd_ck", "o", o, q);
+  TORCH_CHECK(grad_out.sizes() == q.sizes() && o.sizes() == q.sizes(),
+              "attn_bwd_ck: grad_out and o must have q's shape");
+  TORCH_CHECK(q.is_contiguous() && k.is_contiguous() && v.is_contiguous() &&
+                  o.is_contiguous() && lse.is_contiguous(),
+              "attn_bwd_ck: q, k, v, o and lse must be contiguous");
+  // the launcher holds per-batch element strides in ck_tile::index_t
+  TORCH_CHECK((int64_t)Hq * S * 128 < (1LL << 31),
+              "attn_bwd_ck: Hq*S*128 does not fit the kernel's 32-bit index");
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() &&
+                  lse.sizes() == at::IntArrayRef({B, Hq, S}) &&
+                  lse.scalar_type() == at::kFloat,
+              "attn_bwd_ck: lse must be fp32 [B,Hq,S] on q's device");
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
   auto go = grad_out.contiguous();
   auto dq = at::empty_like(q);
@@ -463,7 +515,9 @@ std::vector<at::Tensor> attn_bwd_ck(const at::Tensor& grad_out,
   // the knob stays for window-attention experiments): 0=top-left (fwd
   // convention), 1=bottom-right, 2=swapped lr window. KT_CKBWD_PIPE selects the
   // pipeline: 0=std (KRKTRVR IGLP, 32x32x16 warp tiles), 1=trload
-  // (gfx950 transposed-fragment loads, 16x16x32).
+  // (gfx950 transposed-fragment loads, 16x16x32), 2=trload M0=64,
+  // 3=trload N0=64. All four pass the float64 rules of
+  // tests/test_attention_dense.py on gfx950; 3 has no timing on record.
   int mask_mode = 0;
   if (const char* mm = std::getenv("KT_CKBWD_MASK")) mask_mode = atoi(mm);
   // default pipe 1 (gfx950 trload, 311 TF measured) — fastest correct

@@ -6,6 +6,7 @@ import torch
 
 from kubetorch_amd.models import Llama, llama_tiny
 from kubetorch_amd.parallel import FlatDDP
+from test_model_float64 import assert_logits_rule, logits_references
 
 
 def _tiny_model(device="cpu"):
@@ -98,7 +99,17 @@ def test_loss_step_gpu():
 
 @pytest.mark.gpu
 def test_gpu_forward_matches_cpu():
-    """GPU model (HIP kernels) vs the same weights on CPU (fp32 reference path)."""
+    """GPU model (HIP kernels) vs the same weights on CPU (fp32 reference
+    path), and vs the float64 reference of test_model_float64.py under its
+    logits rule: every row at most as far from float64 as the naive bf16
+    composition's worst row, the whole tensor no noisier and no more biased.
+
+    The assert_close alone cannot tie the GPU model to the reference path:
+    these logits have a standard deviation of 0.33 and a maximum of 1.4, and
+    at rtol=5e-2, atol=5e-1 the model still passed with RoPE removed
+    entirely (cos=1, sin=0: max logit difference 0.049) and with the SwiGLU
+    output multiplied by 1.3 (max difference 0.24). The logits rule rejects
+    both (test_model_float64.py::test_rule_catches_wrong_models)."""
     model, cfg = _tiny_model("cuda")
     cpu_model, _ = _tiny_model("cpu")
     cpu_model.load_state_dict({k: v.cpu() for k, v in model.state_dict().items()})
@@ -107,6 +118,8 @@ def test_gpu_forward_matches_cpu():
         lg = model(x).float().cpu()
         lc = cpu_model(x.cpu()).float()
     torch.testing.assert_close(lg, lc, rtol=5e-2, atol=5e-1)
+    ref64, base = logits_references(model.state_dict(), cfg, x)
+    assert_logits_rule("tiny/forward", lg, ref64, base)
 
 
 def test_generate_kv_cache_matches_recompute():
@@ -148,7 +161,15 @@ def test_generate_sampling_and_stop():
 @pytest.mark.gpu
 def test_generate_gpu_cache_logits_match():
     """bf16 GPU decode: per-step cached logits vs full-recompute logits.
-    (argmax equality is not robust in bf16, so compare the logits.)"""
+    (argmax equality is not robust in bf16, so compare the logits.)
+
+    Cached and recomputed logits are also held to the float64 reference of
+    test_model_float64.py under its logits rule. The assert_close alone
+    compares the GPU model with itself, and at rtol=5e-2, atol=5e-1 on
+    logits of standard deviation 0.33 even the comparison with the CPU path
+    passed with RoPE removed (max logit difference 0.049) and with the
+    SwiGLU output multiplied by 1.3 (max difference 0.24); the logits rule
+    rejects both (test_model_float64.py::test_rule_catches_wrong_models)."""
     model, cfg = _tiny_model("cuda")
     model.eval()
     B, S0 = 2, 7
@@ -167,6 +188,14 @@ def test_generate_gpu_cache_logits_match():
         lg_full2 = model(toks)[:, -1]
         torch.testing.assert_close(lg_cache2.float(), lg_full2.float(),
                                    rtol=5e-2, atol=5e-1)
+        ref64, base = logits_references(model.state_dict(), cfg, toks)
+        rows = torch.arange(B)
+        for tag, got, pos in (("prefill", lg_cache, S0 - 1),
+                              ("prefill_full", lg_full, S0 - 1),
+                              ("step", lg_cache2, S0),
+                              ("step_full", lg_full2, S0)):
+            assert_logits_rule(f"tiny/cache_{tag}", got, ref64, base,
+                               rows=(rows, torch.full((B,), pos)))
     out = model.generate(prompt, max_new_tokens=4)
     assert out.shape == (B, S0 + 4) and out.is_cuda
 

@@ -11,6 +11,7 @@ on one GPU. Usage:
     python bench_decode.py ... --kv paged --prefix-cache --shared-prefix 2048
     python bench_decode.py ... --sampler fused --temperature 0.8 --top-k 50 \
         --top-p 0.9
+    python bench_decode.py ... --weight-dtype fp8
 
 --kv slot (default) is the padded slot cache; --kv paged the block-table
 page pools with the fused decode-attention kernel. --num-splits 0 lets the
@@ -24,6 +25,9 @@ warm-up left. ttft_ms is the wall time of the first step() (all prefills
 plus one decode step), device-synchronised. --sampler fused picks each
 step's tokens with ops.sample_tokens (one call and one host copy per step);
 --top-k and --top-p need it. --temperature applies to either sampler.
+--weight-dtype fp8 quantises the model's linear weights in place after it is
+built (models.quantize_weights_fp8: e4m3 bytes, the skinny-M decode kernel);
+every other flag combines with it.
 """
 import argparse
 import json
@@ -125,6 +129,8 @@ def main():
                          "runs; one engine serves all runs")
     ap.add_argument("--sampler", default="torch", choices=["torch", "fused"],
                     help="fused: one ops.sample_tokens call per step")
+    ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
+                    help="fp8: e4m3 weight-only linears (W8A16)")
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--top-k", type=int, default=0,
                     help="needs --sampler fused")
@@ -140,6 +146,10 @@ def main():
 
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model, cfg = build_model(args.model, dev)
+    if args.weight_dtype == "fp8":
+        from kubetorch_amd.models import quantize_weights_fp8
+
+        model = quantize_weights_fp8(model, inplace=True)
     run = (model, cfg, args.batch, args.prompt, args.new)
     mode = dict(kv=args.kv, page_size=args.page_size,
                 num_splits=args.num_splits)
@@ -177,6 +187,8 @@ def main():
             more["hit_tokens"] = eng.prefix_stats["hit_tokens"] - hit0
     if args.kv_dtype == "fp8":
         more["kv_dtype"] = "fp8"
+    if args.weight_dtype == "fp8":
+        more["weight_dtype"] = "fp8"
     if args.sampler != "torch" or "sampling" in extra:
         more.update(sampler=args.sampler, temperature=args.temperature,
                     top_k=args.top_k, top_p=args.top_p)

@@ -12,4 +12,8 @@ from kubetorch_amd.models.paged_kv import (  # noqa: F401
     PagedKVCache,
     calibrate_kv_scales,
 )
+from kubetorch_amd.models.quantize import (  # noqa: F401
+    dequantize_weights,
+    quantize_weights_fp8,
+)
 from kubetorch_amd.models.serving import BatchedGenerator  # noqa: F401

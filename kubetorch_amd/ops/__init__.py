@@ -1368,6 +1368,222 @@ class Linear(torch.nn.Linear):
 
 
 # ---------------------------------------------------------------------------
+# FP8 weight-only linear (W8A16, serving decode). Inference-only.
+#
+# Format: weight_q [out, in] torch.float8_e4m3fn (OCP e4m3), row-major like
+# nn.Linear.weight, and one static fp32 scale per output row that is a power
+# of two: scale[n] = 2^ceil(log2(amax_n / 448)). The represented matrix is
+# Wq = float(weight_q) * scale[:, None]; with a power-of-two scale every
+# element of Wq is exactly a bf16 value, so the kernel, the composition below
+# and a plain bf16 model holding Wq all multiply by the same matrix and
+# differ in accumulation order only.
+# ---------------------------------------------------------------------------
+W8_DTYPE = torch.float8_e4m3fn
+W8_MAX = 448.0
+W8_SCALE_EXP = 40          # scales lie in [2^-40, 2^40]
+W8_MAX_ROWS = 32           # the kernel's M; more rows run the composition
+W8_K_MULTIPLE = 128
+
+
+def _check_w8_scale_values(scale):
+    """Host check of scale values (a device tensor is copied over, which
+    syncs: call this at construction, not per step)."""
+    s = scale.detach().to("cpu", torch.float32)
+    mant, exp = torch.frexp(s)
+    ok = s.isfinite() & (s > 0) & (mant == 0.5) \
+        & (exp - 1 >= -W8_SCALE_EXP) & (exp - 1 <= W8_SCALE_EXP)
+    if not bool(ok.all()):
+        raise ValueError("weight_scale must be finite, positive powers of "
+                         f"two in [2^-{W8_SCALE_EXP}, 2^{W8_SCALE_EXP}]")
+
+
+def _check_w8(weight_q, weight_scale):
+    """Dtype, shape and device of a quantised weight; the scale values only
+    where looking is no device sync (on the CPU)."""
+    if not torch.is_tensor(weight_q) or weight_q.dtype != W8_DTYPE:
+        raise ValueError("weight_q must be torch.float8_e4m3fn, got "
+                         f"{getattr(weight_q, 'dtype', type(weight_q))}")
+    if weight_q.dim() != 2:
+        raise ValueError("weight_q must be [out_features, in_features]")
+    if not torch.is_tensor(weight_scale) \
+            or weight_scale.dtype != torch.float32:
+        raise ValueError("weight_scale must be fp32")
+    if tuple(weight_scale.shape) != (weight_q.shape[0],):
+        raise ValueError("weight_scale must be [out_features], got "
+                         f"{tuple(weight_scale.shape)}")
+    if weight_scale.device != weight_q.device:
+        raise ValueError("weight_q and weight_scale must be on one device")
+    if not weight_scale.is_cuda:
+        _check_w8_scale_values(weight_scale)
+
+
+def quantize_weight_fp8(w):
+    """[out, in] floating-point weight -> (weight_q e4m3, weight_scale fp32).
+
+    scale[n] is the smallest power of two with amax_n / scale[n] <= 448
+    (2^ceil(log2(amax_n / 448)), computed exactly from the exponent of
+    amax_n, clamped to [2^-40, 2^40]); an all-zero row gets 1.0. Then
+    q = (w.float() * (1 / scale)[:, None]).clamp(-448, 448).to(e4m3): the
+    multiply is exact, the conversion rounds to nearest even. The row maxima
+    of |q| land in (224, 448]; no NaN byte is produced."""
+    if not torch.is_tensor(w) or w.dim() != 2 or not w.is_floating_point() \
+            or w.dtype in _FLOAT8_DTYPES:
+        raise ValueError("w must be a 2-D floating-point weight [out, in]")
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1) if wf.shape[1] else wf.new_zeros(wf.shape[0])
+    if not bool(amax.isfinite().all()):
+        raise ValueError("w holds NaN or inf")
+    # amax = m * 2^e with m in [0.5, 1) and 448 = 0.875 * 2^9, so
+    # amax <= 448 * 2^p  <=>  p >= e - 9 (m <= 0.875) or e - 8 (m > 0.875)
+    mant, exp = torch.frexp(amax)
+    p = exp - 9 + (mant > 0.875).to(exp.dtype)
+    p = p.clamp(-W8_SCALE_EXP, W8_SCALE_EXP)
+    scale = torch.ldexp(torch.ones_like(amax), p)
+    scale = torch.where(amax == 0, torch.ones_like(scale), scale)
+    q = (wf * scale.reciprocal()[:, None]).clamp(-W8_MAX, W8_MAX).to(W8_DTYPE)
+    return q, scale
+
+
+def dequantize_weight_fp8(weight_q, weight_scale, dtype=torch.bfloat16):
+    """Wq = float(weight_q) * weight_scale[:, None] as `dtype`: exact in
+    bf16, fp32 and fp64 (e4m3 has at most 4 significant bits and the scale
+    only shifts the exponent), rounded once for any other dtype."""
+    _check_w8(weight_q, weight_scale)
+    if dtype in (torch.bfloat16, torch.float32, torch.float64):
+        # one temporary of the result's size; the product is exact
+        return weight_q.to(dtype).mul_(weight_scale.to(dtype)[:, None])
+    return (weight_q.float() * weight_scale[:, None]).to(dtype)
+
+
+def _w8_rows(x, K):
+    """x [..., K] as a 2-D [M, K] view, or None where that needs a copy."""
+    if x.dim() == 2:
+        return x
+    try:
+        return x.view(-1, K)
+    except RuntimeError:
+        return None
+
+
+def _linear_w8_kernel_ok(x, weight_q, weight_scale):
+    """What the kernel takes; everything else runs the composition."""
+    K = weight_q.shape[1]
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and K >= W8_K_MULTIPLE
+            and K % W8_K_MULTIPLE == 0 and K <= 1 << 24
+            and 1 <= weight_q.shape[0] <= 1 << 30
+            and weight_q.is_contiguous()):
+        return False
+    x2 = _w8_rows(x, K)
+    if x2 is None:
+        return False
+    M = x2.shape[0]
+    return (1 <= M <= W8_MAX_ROWS and x2.stride(1) == 1
+            and x2.data_ptr() % 16 == 0
+            and (M == 1 or (0 <= x2.stride(0) <= 1 << 24
+                            and x2.stride(0) % 8 == 0)))
+
+
+def linear_w8_splits(out_features, in_features):
+    """The split-K factor the kernel chooses for an [out, in] weight: a
+    function of the shape alone, never of the batch or of device data."""
+    return int(_ext().linear_w8_splits(out_features, in_features))
+
+
+def linear_w8(x, weight_q, weight_scale, num_splits=None):
+    """y[..., n] = round_to_x_dtype(sum_k float(x[..., k]) * Wq[n, k]) with
+    Wq = float(weight_q) * weight_scale[:, None] (quantize_weight_fp8):
+    fp32 accumulation in an order the implementation chooses, one rounding
+    at the end. x is [..., K]; the leading dimensions flatten to M rows.
+    Inference-only: x must not require grad while grad is enabled.
+
+    bf16 GPU x with 1 <= M <= 32, K % 128 == 0, a contiguous last dim,
+    16-byte aligned rows and a contiguous weight_q runs the gfx950 kernel
+    (weights streamed once as fp8, bit-identical run to run, a row's result
+    independent of the other rows in the call). Any other valid input, the
+    CPU included, runs F.linear(x, dequantize_weight_fp8(q, scale, x.dtype)),
+    whose temporary comes from the caching allocator. num_splits overrides
+    the kernel's split-K factor (tests); the composition ignores it.
+
+    Wrong dtypes (weight_q not float8_e4m3fn, weight_scale not fp32), wrong
+    shapes and mismatched devices raise. Scale values are checked on the CPU
+    only (LinearW8 checks them once at construction)."""
+    _check_w8(weight_q, weight_scale)
+    if not torch.is_tensor(x) or not x.is_floating_point() \
+            or x.dtype in _FLOAT8_DTYPES:
+        raise ValueError("x must be a floating-point tensor")
+    N, K = weight_q.shape
+    if x.dim() < 1 or x.shape[-1] != K:
+        raise ValueError(f"x must be [..., {K}], got {tuple(x.shape)}")
+    if x.device != weight_q.device:
+        raise ValueError(f"x is on {x.device}, the weight on "
+                         f"{weight_q.device}")
+    if num_splits is not None and not 1 <= int(num_splits) <= 64:
+        raise ValueError("num_splits must be in [1, 64]")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("linear_w8 is inference-only: x requires grad")
+    if _linear_w8_kernel_ok(x, weight_q, weight_scale):
+        y = _ext().linear_w8(_w8_rows(x, K), weight_q,
+                             weight_scale.contiguous(), int(num_splits or 0))
+        return y.view(*x.shape[:-1], N)
+    return torch.nn.functional.linear(
+        x, dequantize_weight_fp8(weight_q, weight_scale, x.dtype))
+
+
+class LinearW8(torch.nn.Module):
+    """Bias-free linear layer with FP8 weights (ops.linear_w8). weight_q
+    [out, in] e4m3 and weight_scale [out] fp32 are buffers: state_dict,
+    load_state_dict and .to(device) carry them; a dtype cast of the model
+    (.to(torch.bfloat16), .half()) leaves them as they are."""
+
+    def __init__(self, in_features, out_features, device=None):
+        super().__init__()
+        self.in_features = in_features
+        self.out_features = out_features
+        self.register_buffer("weight_q", torch.zeros(
+            out_features, in_features, dtype=W8_DTYPE, device=device))
+        self.register_buffer("weight_scale", torch.ones(
+            out_features, dtype=torch.float32, device=device))
+
+    @classmethod
+    def from_quantized(cls, weight_q, weight_scale):
+        """Wrap an existing (weight_q, weight_scale) pair; the scale values
+        are validated on the host here, once."""
+        _check_w8(weight_q, weight_scale)
+        _check_w8_scale_values(weight_scale)
+        mod = cls(weight_q.shape[1], weight_q.shape[0], device="meta")
+        mod.weight_q = weight_q.contiguous()
+        mod.weight_scale = weight_scale.contiguous()
+        return mod
+
+    @classmethod
+    def from_linear(cls, lin):
+        """Quantise an nn.Linear (ops.Linear included) without bias."""
+        if not isinstance(lin, torch.nn.Linear):
+            raise TypeError(f"expected nn.Linear, got {type(lin).__name__}")
+        if lin.bias is not None:
+            raise ValueError("LinearW8 is bias-free: the layer has a bias")
+        return cls.from_quantized(*quantize_weight_fp8(lin.weight))
+
+    def _apply(self, fn, recurse=True):
+        # device moves apply; dtype casts must not touch the fp8 bytes or
+        # round the scale
+        q, s = self.weight_q, self.weight_scale
+        super()._apply(fn, recurse)
+        if self.weight_q.dtype != W8_DTYPE:
+            self.weight_q = q.to(self.weight_q.device)
+        if self.weight_scale.dtype != torch.float32:
+            self.weight_scale = s.to(self.weight_scale.device)
+        return self
+
+    def forward(self, x):
+        return linear_w8(x, self.weight_q, self.weight_scale)
+
+    def extra_repr(self):
+        return (f"in_features={self.in_features}, "
+                f"out_features={self.out_features}, weight=e4m3")
+
+
+# ---------------------------------------------------------------------------
 # Fused AdamW on flat bf16 buckets (used by kubetorch_amd.parallel)
 # ---------------------------------------------------------------------------
 def adamw_(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):

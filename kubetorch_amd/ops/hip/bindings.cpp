@@ -95,6 +95,10 @@ void kt_sample_tokens(const void* logits, long row_stride, int B, int V,
                       const void* temperature, const void* top_k,
                       const void* top_p, const void* seed, const void* offset,
                       void* out, hipStream_t stream);
+int kt_linear_w8_plan(long N, long K);
+void kt_linear_w8(const void* x, long x_stride, const void* wq,
+                  const void* scale, void* y, void* part, int M, int N, int K,
+                  int S, hipStream_t stream);
 }
 
 namespace {
@@ -884,6 +888,53 @@ at::Tensor sample_tokens(const at::Tensor& logits,
   return out;
 }
 
+at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq,
+                     const at::Tensor& scale, int64_t num_splits) {
+  // x: [M, K] bf16, 1 <= M <= 32, last dim contiguous, row base and stride
+  // 16 B aligned; wq: [N, K] e4m3 contiguous, K % 128 == 0; scale: [N] fp32
+  // (ops.linear_w8 sends everything else to the composition). num_splits 0
+  // is the kernel's own choice from (N, K). The scale values are not looked
+  // at here (that would be a device sync).
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
+              "x must be [M, K] bf16 on GPU");
+  TORCH_CHECK(wq.is_cuda() && wq.device() == x.device() &&
+                  wq.scalar_type() == at::kFloat8_e4m3fn && wq.dim() == 2 &&
+                  wq.is_contiguous(),
+              "weight_q must be [N, K] float8_e4m3fn, contiguous, on x's "
+              "device");
+  const int64_t M = x.size(0), K = x.size(1), N = wq.size(0);
+  TORCH_CHECK(wq.size(1) == K, "x's last dim must be weight_q's K");
+  TORCH_CHECK(scale.is_cuda() && scale.device() == x.device() &&
+                  scale.scalar_type() == at::kFloat && scale.dim() == 1 &&
+                  scale.size(0) == N && scale.is_contiguous(),
+              "weight_scale must be [N] fp32, contiguous, on x's device");
+  TORCH_CHECK(M >= 1 && M <= 32, "M must be in [1, 32], got ", M);
+  TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24),
+              "K must be a multiple of 128 up to 2^24, got ", K);
+  TORCH_CHECK(N >= 1 && N <= (1 << 30), "N must be in [1, 2^30], got ", N);
+  const int64_t xs = M > 1 ? x.stride(0) : K;
+  TORCH_CHECK(x.stride(1) == 1, "x's last dim must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  xs >= 0 && xs % 8 == 0 && xs <= (1 << 24),
+              "x rows must be 16-byte aligned, with a stride up to 2^24");
+  TORCH_CHECK(num_splits >= 0 && num_splits <= 64,
+              "num_splits must be in [0, 64], got ", num_splits);
+  const int S = num_splits > 0 ? (int)num_splits : kt_linear_w8_plan(N, K);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  auto y = at::empty({M, N}, x.options());
+  at::Tensor part;
+  if (S > 1) part = at::empty({S, M, N}, x.options().dtype(at::kFloat));
+  kt_linear_w8(x.data_ptr(), (long)xs, wq.data_ptr(), scale.data_ptr(),
+               y.data_ptr(), S > 1 ? part.data_ptr() : nullptr, (int)M, (int)N,
+               (int)K, S, cur_stream(x));
+  return y;
+}
+
+int64_t linear_w8_splits(int64_t N, int64_t K) {
+  TORCH_CHECK(N >= 1 && K >= 128 && K % 128 == 0, "bad [N, K]");
+  return kt_linear_w8_plan(N, K);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -931,4 +982,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "Causal GQA attention of packed query tokens over a paged KV cache");
   mod.def("sample_tokens", &sample_tokens,
           "Per-row temperature / top-k / top-p / seeded token sampling");
+  mod.def("linear_w8", &linear_w8,
+          "y = x @ (e4m3 weight * scale)^T for M <= 32 rows of bf16 x");
+  mod.def("linear_w8_splits", &linear_w8_splits,
+          "The split-K factor linear_w8 chooses for an [N, K] weight");
 }

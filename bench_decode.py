@@ -11,6 +11,7 @@ on one GPU. Usage:
     python bench_decode.py ... --kv paged --prefix-cache --shared-prefix 2048
     python bench_decode.py ... --sampler fused --temperature 0.8 --top-k 50 \
         --top-p 0.9
+    python bench_decode.py ... --sampler fused --logprobs 5
     python bench_decode.py ... --weight-dtype fp8
 
 --kv slot (default) is the padded slot cache; --kv paged the block-table
@@ -25,6 +26,9 @@ warm-up left. ttft_ms is the wall time of the first step() (all prefills
 plus one decode step), device-synchronised. --sampler fused picks each
 step's tokens with ops.sample_tokens (one call and one host copy per step);
 --top-k and --top-p need it. --temperature applies to either sampler.
+--logprobs N (needs --sampler fused) makes every request record each token's
+log-probability, rank and N alternatives (ops.token_logprobs after every
+sampler call, one more host copy per step).
 --weight-dtype fp8 quantises the model's linear weights in place after it is
 built (models.quantize_weights_fp8: e4m3 bytes, the skinny-M decode kernel);
 every other flag combines with it.
@@ -55,7 +59,7 @@ def build_model(name, dev):
 
 def make_engine(model, batch, prompt, new, kv="slot", page_size=16,
                 num_splits=0, prefill="cache", prefix_cache=False,
-                kv_dtype="bf16", sampler="torch"):
+                kv_dtype="bf16", sampler="torch", logprobs=None):
     from kubetorch_amd.models import BatchedGenerator
 
     kw = {}
@@ -67,6 +71,8 @@ def make_engine(model, batch, prompt, new, kv="slot", page_size=16,
         kw.update(kv_dtype="fp8")
     if sampler != "torch":
         kw.update(sampler=sampler)
+    if logprobs is not None:
+        kw.update(logprobs=logprobs)
     return BatchedGenerator(model, max_batch=batch, max_len=prompt + new + 8,
                             **kw)
 
@@ -91,6 +97,7 @@ def run_once(dev, model, cfg, batch, prompt, new, eng=None, shared=None,
         torch.cuda.synchronize()
     ttft = time.perf_counter() - t0
     out = eng.run()
+    eng.logprobs.clear()
     return sum(len(v) - prompt for v in out.values()), ttft
 
 
@@ -136,9 +143,15 @@ def main():
                     help="needs --sampler fused")
     ap.add_argument("--top-p", type=float, default=1.0,
                     help="needs --sampler fused")
+    ap.add_argument("--logprobs", type=int, default=None,
+                    help="record N alternatives per token (0..32); needs "
+                         "--sampler fused")
     args = ap.parse_args()
     if args.sampler != "fused" and (args.top_k != 0 or args.top_p != 1.0):
         ap.error("--top-k and --top-p need --sampler fused")
+    if args.logprobs is not None and (args.sampler != "fused"
+                                      or not 0 <= args.logprobs <= 32):
+        ap.error("--logprobs needs --sampler fused and a value in [0, 32]")
     if not 0 <= args.shared_prefix <= args.prompt:
         ap.error("--shared-prefix must be in [0, --prompt]")
     if args.kv_dtype == "fp8" and args.kv != "paged":
@@ -165,6 +178,9 @@ def main():
     if args.top_k != 0 or args.top_p != 1.0:
         extra.setdefault("sampling", {}).update(top_k=args.top_k,
                                                 top_p=args.top_p)
+    if args.logprobs is not None:
+        mode.update(logprobs=args.logprobs)
+        extra.setdefault("sampling", {}).update(logprobs=args.logprobs)
     eng = None
     if args.shared_prefix:
         gen = torch.Generator().manual_seed(1)
@@ -192,6 +208,8 @@ def main():
     if args.sampler != "torch" or "sampling" in extra:
         more.update(sampler=args.sampler, temperature=args.temperature,
                     top_k=args.top_k, top_p=args.top_p)
+    if args.logprobs is not None:
+        more["logprobs"] = args.logprobs
     print(json.dumps({
         "metric": "decode_tokens_per_sec",
         "value": round(new_toks / dt, 2),

@@ -44,6 +44,13 @@ and seed; a counter-based draw, so a request's tokens do not depend on its
 batch mates) and one copy of the token ids to the host, in place of one
 host-side `_sample` and sync per request. Under a graph the call is part of
 the captured step. The default, sampler="torch", is `_sample` as it was.
+
+`logprobs=N` (opt-in, needs sampler="fused") follows every sampler call with
+one ops.token_logprobs call on the same logits rows, the returned tokens and
+the rows' temperatures: the log-probability and rank of each generated token
+and up to N alternatives, for the requests that ask (`submit(logprobs=n)`).
+The four outputs travel to the host as one packed tensor, one copy more per
+step. A finished request's record appears in `eng.logprobs[rid]`.
 """
 from dataclasses import dataclass, field
 
@@ -65,6 +72,8 @@ class _Request:
     top_k: int = 0                # sampler="fused" only, as is what follows
     top_p: float = 1.0
     seed: int = 0
+    logprobs: int = None          # alternatives per token; None: no record
+    lp: dict = None               # the record, filled by _emit_token
 
 
 class BatchedGenerator:
@@ -72,12 +81,25 @@ class BatchedGenerator:
                  prefill_chunk=None, graph=None, kv="slot", page_size=16,
                  num_pages=None, num_splits=None, prefill="cache",
                  prefix_cache=False, kv_dtype=None, kv_scales=None,
-                 sampler="torch", sampler_seed=0):
+                 sampler="torch", sampler_seed=0, logprobs=None):
         if sampler not in ("torch", "fused"):
             raise ValueError(
                 f"sampler must be 'torch' or 'fused', got {sampler!r}")
         self._fused = sampler == "fused"
         self._sampler_seed = int(sampler_seed)
+        if logprobs is not None:
+            if not self._fused:
+                raise ValueError("logprobs needs sampler='fused'")
+            if not isinstance(logprobs, int) or isinstance(logprobs, bool) \
+                    or not 0 <= logprobs <= ops.LOGPROBS_MAX_TOP:
+                raise ValueError(
+                    f"logprobs must be None or an int in "
+                    f"[0, {ops.LOGPROBS_MAX_TOP}], got {logprobs!r}")
+        # None: no ops.token_logprobs call anywhere; N: top_n of every call
+        self._lp_n = logprobs
+        # rid -> record of a finished request that asked for one (the caller
+        # pops entries; the most recent 4096 rids are kept)
+        self.logprobs = {}
         if kv not in ("slot", "paged"):
             raise ValueError(f"kv must be 'slot' or 'paged', got {kv!r}")
         if kv_dtype not in (None, "fp8"):
@@ -174,12 +196,30 @@ class BatchedGenerator:
 
     # -- client API ----------------------------------------------------------
     def submit(self, prompt_ids, max_new_tokens=32, temperature=0.0,
-               stop_token=None, top_k=0, top_p=1.0, seed=None):
+               stop_token=None, top_k=0, top_p=1.0, seed=None,
+               logprobs=None):
         """Queue a request; returns its id. top_k, top_p and seed need
         sampler="fused" (ops.sample_tokens has their meaning): top_k=0 and
         top_p=1.0 are off, seed=None is (sampler_seed << 32) | rid, so a
         fresh engine given the same submissions repeats its outputs. A
-        request's tokens depend on its seed, never on its batch mates."""
+        request's tokens depend on its seed, never on its batch mates.
+
+        logprobs=n (0 <= n <= the engine's logprobs=N) records, for every
+        generated token, its log-probability and rank and the n most likely
+        tokens with theirs (ops.token_logprobs has their meaning: the
+        distribution at the request's temperature before top-k / top-p).
+        When the request finishes the record is eng.logprobs[rid]: a dict
+        of tokens, logprobs, ranks, top_ids and top_logprobs, one entry per
+        generated token."""
+        if logprobs is not None:
+            if self._lp_n is None:
+                raise ValueError(
+                    "logprobs needs an engine built with logprobs=N")
+            if not isinstance(logprobs, int) or isinstance(logprobs, bool) \
+                    or not 0 <= logprobs <= self._lp_n:
+                raise ValueError(
+                    f"logprobs must be None or an int in [0, {self._lp_n}], "
+                    f"got {logprobs!r}")
         if not self._fused:
             if top_k != 0 or top_p != 1.0 or seed is not None:
                 raise ValueError(
@@ -202,7 +242,7 @@ class BatchedGenerator:
         self.pending.append(_Request(rid, prompt, max_new_tokens,
                                      temperature, stop_token,
                                      top_k=int(top_k), top_p=float(top_p),
-                                     seed=seed))
+                                     seed=seed, logprobs=logprobs))
         return rid
 
     @property
@@ -283,7 +323,8 @@ class BatchedGenerator:
         for s0 in range(0, S0, chunk):
             logits = self.model._forward_cached(batch[:, s0:s0 + chunk],
                                                 cache)
-        toks = self._sample_rows(group, logits) if self._fused else None
+        toks, recs = self._sample_rows(group, logits) if self._fused \
+            else (None, None)
         for j, req in enumerate(group):
             self._store_prefill(req, cache, j, S0)
             self.lens[req.slot] = S0
@@ -292,7 +333,7 @@ class BatchedGenerator:
             if toks is None:
                 self._emit(req, logits[j])
             else:
-                self._emit_token(req, toks[j])
+                self._emit_token(req, toks[j], recs and recs[j])
 
     def _store_prefill(self, req, cache, j, S0):
         """Move row j of a prefill cache into the request's slot (slot
@@ -346,15 +387,17 @@ class BatchedGenerator:
                 max(b - a for a, b in zip(cu, cu[1:])),
                 torch.tensor(last).to(dev))
             rest = []
-            toks = {}
+            toks, recs = {}, None
             if self._fused:  # one call for the rows whose prompt is in
                 fin = [j for j, r in enumerate(todo)
                        if done[r.rid] >= r.prompt.numel()]
                 if fin:
                     rows = logits if len(fin) == len(todo) else \
                         logits[torch.tensor(fin).to(dev)]
-                    toks = dict(zip(fin, self._sample_rows(
-                        [todo[j] for j in fin], rows)))
+                    picked, recs = self._sample_rows(
+                        [todo[j] for j in fin], rows)
+                    toks = dict(zip(fin, picked))
+                    recs = recs and dict(zip(fin, recs))
             for j, r in enumerate(todo):
                 S0 = r.prompt.numel()
                 if done[r.rid] < S0:
@@ -366,7 +409,7 @@ class BatchedGenerator:
                 if self._prefix:  # before _emit, which may release the slot
                     self._pkv.publish(r.slot, r.out)
                 if self._fused:
-                    self._emit_token(r, toks[j])
+                    self._emit_token(r, toks[j], recs and recs[j])
                 else:
                     self._emit(r, logits[j])
             todo = rest
@@ -425,19 +468,58 @@ class BatchedGenerator:
 
     def _sample_rows(self, reqs, logits):
         """Row j of logits [len(reqs), vocab] is request j's: one sampler
-        call and one copy to the host -> list of token ids."""
-        return ops.sample_tokens(logits, *self._sample_params(reqs)).tolist()
+        call and one copy to the host -> (list of token ids, the rows'
+        log-prob records or None when no request of the call asked)."""
+        params = self._sample_params(reqs)
+        toks = ops.sample_tokens(logits, *params)
+        recs = None
+        if self._wants_logprobs(reqs):
+            recs = self._logprob_rows(logits, toks, params[0]).tolist()
+        return toks.tolist(), recs
+
+    # -- logprobs=N: ops.token_logprobs after every sampler call -------------
+    def _wants_logprobs(self, reqs):
+        return self._lp_n is not None and any(
+            r is not None and r.logprobs is not None for r in reqs)
+
+    def _logprob_rows(self, logits, toks, temperature):
+        """ops.token_logprobs on the rows a sampler call saw and the tokens
+        it returned, packed for one copy to the host: row j is float64
+        [logprob, rank, N top ids, N top log-probs] (fp32 and int32 values
+        are exact in float64). Capturable."""
+        lp, rank, ids, top = ops.token_logprobs(logits, toks, temperature,
+                                                self._lp_n)
+        B = lp.shape[0]
+        return torch.cat([lp.double().view(B, 1), rank.double().view(B, 1),
+                          ids.double(), top.double()], dim=1)
 
     def _emit(self, req, logits):
         self._emit_token(req, self._sample(req, logits))
 
-    def _emit_token(self, req, nxt):
+    def _emit_token(self, req, nxt, rec=None):
+        """Append token nxt to the request; rec is its packed row of
+        _logprob_rows, of which a request that asked keeps its own n
+        alternatives."""
         req.out.append(nxt)
         req.next_tok = nxt
+        if req.logprobs is not None:
+            if req.lp is None:
+                req.lp = {"tokens": [], "logprobs": [], "ranks": [],
+                          "top_ids": [], "top_logprobs": []}
+            n, N = req.logprobs, self._lp_n
+            req.lp["tokens"].append(nxt)
+            req.lp["logprobs"].append(rec[0])
+            req.lp["ranks"].append(int(rec[1]))
+            req.lp["top_ids"].append([int(i) for i in rec[2:2 + n]])
+            req.lp["top_logprobs"].append(rec[2 + N:2 + N + n])
         done = (len(req.out) - req.prompt.numel() >= req.max_new_tokens
                 or (req.stop_token is not None and nxt == req.stop_token))
         if done:
             self.finished[req.rid] = req.out
+            if req.lp is not None:
+                self.logprobs[req.rid] = req.lp
+                if len(self.logprobs) > 4096:
+                    del self.logprobs[next(iter(self.logprobs))]
             self.slots[req.slot] = None
             self.lens[req.slot] = 0
             self._host_lens[req.slot] = 0
@@ -534,6 +616,11 @@ class BatchedGenerator:
             # slots are greedy rows over garbage and are ignored
             toks = ops.sample_tokens(logits, *self._g_samp)
             self._g_samp[4].add_(self._g_act)  # offset: one more drawn
+            if self._lp_n is not None:
+                # always part of the step, whoever asked: the captured graph
+                # is one for the engine's life
+                return toks, self._logprob_rows(logits, toks,
+                                                self._g_samp[0])
             return toks
         return logits
 
@@ -599,9 +686,14 @@ class BatchedGenerator:
                     buf.copy_(new, non_blocking=True)
                 self._g_owner = owner
             graph.replay()
+            recs = None
+            if self._lp_n is not None:  # the output is (tokens, records)
+                logits, packed = logits
+                if self._wants_logprobs(self.slots):
+                    recs = packed.tolist()
             toks = logits.tolist()  # the graph's output is the tokens
             for s in active:
-                self._emit_token(self.slots[s], toks[s])
+                self._emit_token(self.slots[s], toks[s], recs and recs[s])
             return
         graph.replay()
         for s in active:
@@ -629,10 +721,14 @@ class BatchedGenerator:
                 self._e_samp = (rids, self._sample_params(
                     [self.slots[s] for s in active]))
             params = self._e_samp[1]
-            toks = ops.sample_tokens(logits, *params).tolist()
+            toks = ops.sample_tokens(logits, *params)
             params[4] += 1
+            recs = None
+            if self._wants_logprobs([self.slots[s] for s in active]):
+                recs = self._logprob_rows(logits, toks, params[0]).tolist()
+            toks = toks.tolist()
             for j, s in enumerate(active):
-                self._emit_token(self.slots[s], toks[j])
+                self._emit_token(self.slots[s], toks[j], recs and recs[j])
             return
         for j, s in enumerate(active):
             self._emit(self.slots[s], logits[j])

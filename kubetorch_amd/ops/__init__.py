@@ -1096,6 +1096,120 @@ def sample_tokens(logits, temperature, top_k, top_p, seed, offset):
 
 
 # ---------------------------------------------------------------------------
+# Per-token log-probabilities (serving): what the sampler's pick was worth.
+# Inference-only, no autograd, no host sync on the GPU.
+# ---------------------------------------------------------------------------
+LOGPROBS_MAX_TOP = 32
+
+
+def _token_logprobs_ref(logits, token, temperature, top_n=0,
+                        dtype=torch.float32):
+    """The float64 composition that defines token_logprobs (see there); pure
+    tensor ops on the logits' device. On the GPU nothing is read on the
+    host and a token outside [0, V) gives the sentinels; on the CPU it is a
+    ValueError. dtype=torch.float64 returns the log-probs unrounded."""
+    B, V = logits.shape
+    inf = float("inf")
+    x = logits.double()
+    x = torch.where(x.isnan(), torch.full_like(x, -inf), x)
+    T = temperature.double().view(B, 1)
+    T = torch.where(T > 0, T, torch.ones_like(T))
+    xmax = x.max(dim=1, keepdim=True).values
+    has_pinf = xmax == inf
+    nothing = xmax == -inf
+    edge = has_pinf | nothing
+    a = torch.where(edge, torch.zeros_like(x), x - xmax) / T
+    lp = a - torch.log(torch.exp(a).sum(dim=1, keepdim=True))
+    # a row holding +inf: its +inf entries share the mass
+    n_pinf = (x == inf).sum(dim=1, keepdim=True).double()
+    lp_pinf = torch.where(x == inf, -torch.log(n_pinf),
+                          torch.full_like(x, -inf))
+    lp = torch.where(has_pinf, lp_pinf, lp)
+    # a row with nothing above -inf has no distribution
+    lp = torch.where(nothing, torch.full_like(x, float("nan")), lp)
+    tok = token.view(B, 1)
+    ok = (tok >= 0) & (tok < V)
+    if not logits.is_cuda and not bool(ok.all()):
+        raise ValueError(f"token must be in [0, {V})")
+    tc = tok.clamp(0, V - 1)
+    logprob = torch.where(ok, lp.gather(1, tc),
+                          torch.full_like(xmax, float("nan")))
+    above = (x > x.gather(1, tc)).sum(dim=1, keepdim=True)
+    rank = torch.where(ok, above + 1, torch.zeros_like(above))
+    n = min(top_n, V)
+    top_ids = torch.full((B, top_n), -1, dtype=torch.int32,
+                         device=logits.device)
+    top_lp = torch.full((B, top_n), -inf, dtype=dtype, device=logits.device)
+    if n > 0:
+        # stable: equal logits keep index order, the lowest index first
+        order = x.sort(dim=1, descending=True, stable=True).indices[:, :n]
+        top_ids[:, :n] = order
+        top_lp[:, :n] = lp.gather(1, order)
+    return (logprob.view(B).to(dtype), rank.view(B).to(torch.int32), top_ids,
+            top_lp)
+
+
+def token_logprobs(logits, token, temperature, top_n=0):
+    """For every row of logits [B, V], the log-probability and rank of
+    token [B] int64 under temperature [B] fp32 (both on the logits' device)
+    and the top_n most likely tokens: (logprob [B] fp32, rank [B] int32,
+    top_ids [B, top_n] int32, top_logprobs [B, top_n] fp32). top_n is a host
+    int in [0, 32]; nothing is read on the host, the call makes no sync and
+    can be captured in a graph.
+
+    Per row, from the logits as given:
+      1. NaN counts as -inf. T_eff = T if T > 0 else 1: a greedy row
+         reports the raw distribution.
+      2. a_i = (x_i - max) / T_eff and logprob = a_tok - log(sum_j exp(a_j))
+         over the whole vocabulary. The sampler's top-k and top-p filters
+         are NOT applied: with the filters off this is exactly the
+         distribution the token was drawn from, with them on it is the
+         distribution before filtering.
+      3. rank = 1 + #{j : x_j > x_tok}.
+      4. top_ids are the top_n largest logits, descending, equal logits by
+         the lowest index first; top_logprobs are their log-probs at the
+         same T_eff. Slots past V hold id -1 and -inf.
+      5. A row holding +inf: its +inf entries get -log(their count), all
+         others -inf. A row with nothing above -inf: log-probs are NaN,
+         the ids are the lowest indices.
+      6. A token outside [0, V): on the GPU logprob NaN and rank 0, and
+         nothing is read outside the row; on the CPU a ValueError.
+    A row's result depends on nothing but the row and its own parameters.
+
+    Dispatch is sample_tokens': bf16 GPU logits with V <= 262144 and 16-byte
+    aligned rows run the HIP kernel (fp32 terms summed in fp64 by a fixed
+    tree, bit-identical run to run, for any B and row position); the CPU and
+    every other input run the same rules as a float64 torch composition,
+    which is the reference. Arguments are checked by shape, dtype and device
+    only."""
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError("logits must be [B, V] with V >= 1")
+    if not logits.is_floating_point():
+        raise ValueError("logits must be a floating-point tensor")
+    _no_grad_inputs("token_logprobs", logits)
+    if not isinstance(top_n, int) or isinstance(top_n, bool) \
+            or not 0 <= top_n <= LOGPROBS_MAX_TOP:
+        raise ValueError(
+            f"top_n must be an int in [0, {LOGPROBS_MAX_TOP}], got {top_n!r}")
+    B = logits.shape[0]
+    for name, t, dt in (("token", token, torch.int64),
+                        ("temperature", temperature, torch.float32)):
+        if not torch.is_tensor(t) or t.dtype != dt \
+                or tuple(t.shape) != (B,) or t.device != logits.device:
+            raise ValueError(f"{name} must be [B] {dt} on the logits' device")
+    if B == 0:
+        dev = logits.device
+        return (torch.empty(0, dtype=torch.float32, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty(0, top_n, dtype=torch.int32, device=dev),
+                torch.empty(0, top_n, dtype=torch.float32, device=dev))
+    if _sampler_kernel_ok(logits):
+        return tuple(_ext().token_logprobs(logits, token.contiguous(),
+                                           temperature.contiguous(), top_n))
+    return _token_logprobs_ref(logits, token, temperature, top_n)
+
+
+# ---------------------------------------------------------------------------
 # Multi-tensor pack/unpack (GPU data plane: packed state-dict transfers)
 # ---------------------------------------------------------------------------
 PACK_ALIGN = 16  # bytes; segment starts in the flat buffer are 16B-aligned

@@ -17,7 +17,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 # module name -> sources (each builds an in-tree .so)
 MODULES = {
-    "_hip_ops": ["kernels.hip", "attention.hip", "attention_ck.hip", "attention_ck_bwd.hip", "paged_attention.hip", "paged_prefill.hip", "sampler.hip", "linear_w8.hip", "bindings.cpp"],
+    "_hip_ops": ["kernels.hip", "attention.hip", "attention_ck.hip", "attention_ck_bwd.hip", "paged_attention.hip", "paged_prefill.hip", "sampler.hip", "logprobs.hip", "linear_w8.hip", "bindings.cpp"],
     "_hip_spill": ["spill.cpp"],
 }
 SO_PATH = os.path.join(OPS_DIR, "_hip_ops.so")  # primary (back-compat)

@@ -95,6 +95,10 @@ void kt_sample_tokens(const void* logits, long row_stride, int B, int V,
                       const void* temperature, const void* top_k,
                       const void* top_p, const void* seed, const void* offset,
                       void* out, hipStream_t stream);
+void kt_token_logprobs(const void* logits, long row_stride, int B, int V,
+                       const void* token, const void* temperature, int top_n,
+                       void* logprob, void* rank, void* top_ids,
+                       void* top_logprobs, hipStream_t stream);
 int kt_linear_w8_plan(long N, long K);
 void kt_linear_w8(const void* x, long x_stride, const void* wq,
                   const void* scale, void* y, void* part, int M, int N, int K,
@@ -888,6 +892,55 @@ at::Tensor sample_tokens(const at::Tensor& logits,
   return out;
 }
 
+std::vector<at::Tensor> token_logprobs(const at::Tensor& logits,
+                                       const at::Tensor& token,
+                                       const at::Tensor& temperature,
+                                       int64_t top_n) {
+  // logits as for sample_tokens (ops.token_logprobs sends everything else
+  // to the reference); token [B] int64 and temperature [B] fp32 on the
+  // logits' device. Their values are not looked at here (that would be a
+  // device sync): the kernel reads no logit for a token outside [0, V).
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16 &&
+                  logits.dim() == 2,
+              "logits must be [B, V] bf16 on GPU");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= 262144, "V must be in [1, 262144], got ", V);
+  TORCH_CHECK(B < (int64_t)INT32_MAX, "batch too large");
+  TORCH_CHECK(V == 1 || logits.stride(1) == 1,
+              "logits' last dim must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0 &&
+                  (B <= 1 ||
+                   (logits.stride(0) >= 0 && logits.stride(0) % 8 == 0)),
+              "logits rows must be 16-byte aligned");
+  TORCH_CHECK(top_n >= 0 && top_n <= 32, "top_n must be in [0, 32], got ",
+              top_n);
+  TORCH_CHECK(token.is_cuda() && token.device() == logits.device() &&
+                  token.scalar_type() == at::kLong && token.dim() == 1 &&
+                  token.size(0) == B && token.is_contiguous(),
+              "token must be [B] int64, contiguous, on the logits' device");
+  TORCH_CHECK(temperature.is_cuda() &&
+                  temperature.device() == logits.device() &&
+                  temperature.scalar_type() == at::kFloat &&
+                  temperature.dim() == 1 && temperature.size(0) == B &&
+                  temperature.is_contiguous(),
+              "temperature must be [B] fp32, contiguous, on the logits' "
+              "device");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
+  auto f32 = logits.options().dtype(at::kFloat);
+  auto i32 = logits.options().dtype(at::kInt);
+  auto logprob = at::empty({B}, f32);
+  auto rank = at::empty({B}, i32);
+  auto top_ids = at::empty({B, top_n}, i32);
+  auto top_lp = at::empty({B, top_n}, f32);
+  if (B > 0)
+    kt_token_logprobs(logits.data_ptr(), B > 1 ? (long)logits.stride(0) : 0,
+                      (int)B, (int)V, token.data_ptr(),
+                      temperature.data_ptr(), (int)top_n, logprob.data_ptr(),
+                      rank.data_ptr(), top_ids.data_ptr(), top_lp.data_ptr(),
+                      cur_stream(logits));
+  return {logprob, rank, top_ids, top_lp};
+}
+
 at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq,
                      const at::Tensor& scale, int64_t num_splits) {
   // x: [M, K] bf16, 1 <= M <= 32, last dim contiguous, row base and stride
@@ -982,6 +1035,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "Causal GQA attention of packed query tokens over a paged KV cache");
   mod.def("sample_tokens", &sample_tokens,
           "Per-row temperature / top-k / top-p / seeded token sampling");
+  mod.def("token_logprobs", &token_logprobs,
+          "Per-row log-probability and rank of a token, and the top_n tokens");
   mod.def("linear_w8", &linear_w8,
           "y = x @ (e4m3 weight * scale)^T for M <= 32 rows of bf16 x");
   mod.def("linear_w8_splits", &linear_w8_splits,

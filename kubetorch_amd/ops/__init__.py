@@ -599,6 +599,23 @@ def _check_pools(k_pages, v_pages):
         raise ValueError(f"head_dim must be one of {PAGED_HEAD_DIMS}")
 
 
+def _check_paged_query(q, k_pages, v_pages, fp8, rows, bf16_only):
+    """CPU-path checks shared by paged decode and prefill: the pools, q
+    [rows, Hq, hd] against them, the GQA group and q's dtype. bf16_only:
+    q must be bf16 (or fp32) even next to unquantised pools of its dtype."""
+    _check_pools(k_pages, v_pages)
+    if q.dim() != 3 or q.shape[2] != k_pages.shape[3]:
+        raise ValueError(f"q must be [{rows}, Hq, hd] with the pool's "
+                         "head_dim")
+    Hq, Hkv = q.shape[1], k_pages.shape[1]
+    if Hq % Hkv or Hq // Hkv not in PAGED_GROUPS:
+        raise ValueError(f"group Hq/Hkv must be one of {PAGED_GROUPS}")
+    if bf16_only and q.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("q must be bf16 (fp32 on the CPU reference path)")
+    if not fp8 and (q.dtype != k_pages.dtype or q.dtype != v_pages.dtype):
+        raise ValueError("q and the pools must share a dtype")
+
+
 # fp8 pools: the same layout with torch.float8_e4m3fn (OCP e4m3) elements
 # and static fp32 scales per kv head, k_scale / v_scale [n_kv] on the pools'
 # device (None = 1.0). A stored byte encodes x / scale, the value read back
@@ -805,17 +822,7 @@ def paged_attention_decode(q, k_pages, v_pages, block_table, seq_lens,
                                              seq_lens, float(scale),
                                              int(num_splits), k_scale,
                                              v_scale)
-    _check_pools(k_pages, v_pages)
-    if q.dim() != 3 or q.shape[2] != k_pages.shape[3]:
-        raise ValueError("q must be [B, Hq, hd] with the pool's head_dim")
-    Hq, Hkv = q.shape[1], k_pages.shape[1]
-    if Hq % Hkv or Hq // Hkv not in PAGED_GROUPS:
-        raise ValueError(f"group Hq/Hkv must be one of {PAGED_GROUPS}")
-    if fp8:
-        if q.dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError("q must be bf16 (fp32 on the CPU reference path)")
-    elif q.dtype != k_pages.dtype or q.dtype != v_pages.dtype:
-        raise ValueError("q and the pools must share a dtype")
+    _check_paged_query(q, k_pages, v_pages, fp8, "B", bf16_only=fp8)
     if block_table.dtype != torch.int32 or seq_lens.dtype != torch.int32 \
             or block_table.dim() != 2 or block_table.shape[0] != q.shape[0] \
             or tuple(seq_lens.shape) != (q.shape[0],):
@@ -906,16 +913,7 @@ def paged_attention_prefill(q, k_pages, v_pages, block_table, cu_q_lens,
                                               block_table, cu_q_lens,
                                               seq_lens, int(max_q_len),
                                               float(scale), k_scale, v_scale)
-    _check_pools(k_pages, v_pages)
-    if q.dim() != 3 or q.shape[2] != k_pages.shape[3]:
-        raise ValueError("q must be [T, Hq, hd] with the pool's head_dim")
-    Hq, Hkv = q.shape[1], k_pages.shape[1]
-    if Hq % Hkv or Hq // Hkv not in PAGED_GROUPS:
-        raise ValueError(f"group Hq/Hkv must be one of {PAGED_GROUPS}")
-    if q.dtype != torch.bfloat16 and q.dtype != torch.float32:
-        raise ValueError("q must be bf16 (fp32 on the CPU reference path)")
-    if not fp8 and (q.dtype != k_pages.dtype or q.dtype != v_pages.dtype):
-        raise ValueError("q and the pools must share a dtype")
+    _check_paged_query(q, k_pages, v_pages, fp8, "T", bf16_only=True)
     if block_table.dtype != torch.int32 or block_table.dim() != 2:
         raise ValueError("block_table must be [B, max_blocks] int32")
     B = block_table.shape[0]
@@ -1032,6 +1030,23 @@ def _sample_tokens_ref(logits, temperature, top_k, top_p, seed, offset,
     return token
 
 
+def _check_logits_call(name, logits, vectors):
+    """Argument checks shared by sample_tokens and token_logprobs: logits
+    [B, V] floating point without grad, and each (name, tensor, dtype) of
+    `vectors` a [B] tensor of that dtype on the logits' device. Returns B."""
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError("logits must be [B, V] with V >= 1")
+    if not logits.is_floating_point():
+        raise ValueError("logits must be a floating-point tensor")
+    _no_grad_inputs(name, logits)
+    B = logits.shape[0]
+    for vname, t, dt in vectors:
+        if not torch.is_tensor(t) or t.dtype != dt \
+                or tuple(t.shape) != (B,) or t.device != logits.device:
+            raise ValueError(f"{vname} must be [B] {dt} on the logits' device")
+    return B
+
+
 def _sampler_kernel_ok(logits):
     """What the kernel takes; everything else runs the reference."""
     B, V = logits.shape
@@ -1072,20 +1087,12 @@ def sample_tokens(logits, temperature, top_k, top_p, seed, offset):
     kernel (fp32 scores, bit-identical run to run); the CPU and every other
     input run the same rules as a float64 torch composition, which is the
     reference. Arguments are checked by shape, dtype and device only."""
-    if logits.dim() != 2 or logits.shape[1] < 1:
-        raise ValueError("logits must be [B, V] with V >= 1")
-    if not logits.is_floating_point():
-        raise ValueError("logits must be a floating-point tensor")
-    _no_grad_inputs("sample_tokens", logits)
-    B = logits.shape[0]
-    for name, t, dt in (("temperature", temperature, torch.float32),
-                        ("top_k", top_k, torch.int32),
-                        ("top_p", top_p, torch.float32),
-                        ("seed", seed, torch.int64),
-                        ("offset", offset, torch.int64)):
-        if not torch.is_tensor(t) or t.dtype != dt \
-                or tuple(t.shape) != (B,) or t.device != logits.device:
-            raise ValueError(f"{name} must be [B] {dt} on the logits' device")
+    B = _check_logits_call("sample_tokens", logits, (
+        ("temperature", temperature, torch.float32),
+        ("top_k", top_k, torch.int32),
+        ("top_p", top_p, torch.float32),
+        ("seed", seed, torch.int64),
+        ("offset", offset, torch.int64)))
     if B == 0:
         return torch.empty(0, dtype=torch.long, device=logits.device)
     if _sampler_kernel_ok(logits):
@@ -1182,21 +1189,13 @@ def token_logprobs(logits, token, temperature, top_n=0):
     every other input run the same rules as a float64 torch composition,
     which is the reference. Arguments are checked by shape, dtype and device
     only."""
-    if logits.dim() != 2 or logits.shape[1] < 1:
-        raise ValueError("logits must be [B, V] with V >= 1")
-    if not logits.is_floating_point():
-        raise ValueError("logits must be a floating-point tensor")
-    _no_grad_inputs("token_logprobs", logits)
+    B = _check_logits_call("token_logprobs", logits, (
+        ("token", token, torch.int64),
+        ("temperature", temperature, torch.float32)))
     if not isinstance(top_n, int) or isinstance(top_n, bool) \
             or not 0 <= top_n <= LOGPROBS_MAX_TOP:
         raise ValueError(
             f"top_n must be an int in [0, {LOGPROBS_MAX_TOP}], got {top_n!r}")
-    B = logits.shape[0]
-    for name, t, dt in (("token", token, torch.int64),
-                        ("temperature", temperature, torch.float32)):
-        if not torch.is_tensor(t) or t.dtype != dt \
-                or tuple(t.shape) != (B,) or t.device != logits.device:
-            raise ValueError(f"{name} must be [B] {dt} on the logits' device")
     if B == 0:
         dev = logits.device
         return (torch.empty(0, dtype=torch.float32, device=dev),

@@ -17,7 +17,10 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 # module name -> sources (each builds an in-tree .so)
 MODULES = {
-    "_hip_ops": ["kernels.hip", "attention.hip", "attention_ck.hip", "attention_ck_bwd.hip", "paged_attention.hip", "paged_prefill.hip", "sampler.hip", "logprobs.hip", "linear_w8.hip", "bindings.cpp"],
+    "_hip_ops": ["kernels.hip", "attention.hip", "attention_ck.hip",
+                 "attention_ck_bwd.hip", "paged_attention.hip",
+                 "paged_prefill.hip", "sampler.hip", "logprobs.hip",
+                 "linear_w8.hip", "bindings.cpp"],
     "_hip_spill": ["spill.cpp"],
 }
 SO_PATH = os.path.join(OPS_DIR, "_hip_ops.so")  # primary (back-compat)
@@ -64,12 +67,11 @@ def _needs_rebuild(so_path, sources):
     if not os.path.exists(so_path):
         return True
     so_mtime = os.path.getmtime(so_path)
-    for src in sources + ["build.py"]:
-        p = (os.path.join(HIP_DIR, src) if src != "build.py"
-             else os.path.join(OPS_DIR, src))
-        if os.path.getmtime(p) > so_mtime:
-            return True
-    return False
+    # any header may be included by any source
+    headers = [f for f in os.listdir(HIP_DIR) if f.endswith(".h")]
+    deps = [os.path.join(HIP_DIR, f) for f in sources + headers]
+    deps.append(os.path.join(OPS_DIR, "build.py"))
+    return any(os.path.getmtime(p) > so_mtime for p in deps)
 
 
 def _build_module(name, sources, verbose, force):

@@ -20,14 +20,14 @@
 #include <hip/hip_runtime.h>
 #include <rocwmma/rocwmma.hpp>
 
+#include "device_common.h"
+#include "kt_launchers.h"
+
 using rocwmma::accumulator;
 using rocwmma::col_major;
 using rocwmma::matrix_a;
 using rocwmma::matrix_b;
 using rocwmma::row_major;
-
-typedef unsigned short u16;
-typedef ushort vec8u __attribute__((ext_vector_type(8)));
 
 #define WAVE 64
 #define QT 128     // q rows per workgroup (32 per wave = 2 row-blocks)
@@ -43,12 +43,6 @@ using FragKt = rocwmma::fragment<matrix_b, 16, 16, 32, rocwmma::bfloat16_t, col_
 using FragP = rocwmma::fragment<matrix_a, 16, 16, 32, rocwmma::bfloat16_t, row_major>;
 using FragV = rocwmma::fragment<matrix_b, 16, 16, 32, rocwmma::bfloat16_t, row_major>;
 using FragAcc = rocwmma::fragment<accumulator, 16, 16, 32, float>;
-
-__device__ __forceinline__ u16 f2bf(float f) {
-  unsigned int u = __float_as_uint(f);
-  u += 0x7fff + ((u >> 16) & 1);
-  return (u16)(u >> 16);
-}
 
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const u16* __restrict__ q, const u16* __restrict__ k,

@@ -15,6 +15,8 @@
 #include <ck_tile/ops/fmha.hpp>
 #include <ck_tile/ops/fmha_fwd_v3_impl.hpp>
 
+#include "kt_launchers.h"
+
 namespace {
 
 using qkv_t = ck_tile::bf16_t;

@@ -23,6 +23,8 @@
 #include <ck_tile/ops/epilogue.hpp>
 #include <ck_tile/ops/fmha.hpp>
 
+#include "kt_launchers.h"
+
 namespace {
 
 using bf16 = ck_tile::bf16_t;

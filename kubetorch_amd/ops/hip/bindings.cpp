@@ -12,98 +12,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
-extern "C" {
-void kt_rmsnorm_fwd(const void* x, const void* res, const void* w, void* y,
-                    void* s_out, void* invrms, int N, int H, float eps,
-                    hipStream_t stream);
-void kt_rmsnorm_bwd(const void* dy, const void* ds, const void* x,
-                    const void* w, const void* invrms, void* dx,
-                    void* dw_partial, void* dw, int P, int N, int H,
-                    hipStream_t stream);
-void kt_rope(const void* x, void* o, const void* cost, const void* sint,
-             long total_quads, int S, int Hh, int D, long src_t_stride,
-             long src_h_stride, float sign, float oscale, hipStream_t stream);
-void kt_attn_grad_pack(const void* dq, const void* dk, const void* dv,
-                       void* out, const void* cost, const void* sint, long B,
-                       int S, int Hq, int Hkv, int D, const long* strides,
-                       float oscale, hipStream_t stream);
-void kt_swiglu_fwd(const void* gu, void* out, long N, int I,
-                   hipStream_t stream);
-void kt_swiglu_bwd(const void* dout, const void* gu, void* dgu, long N, int I,
-                   hipStream_t stream);
-void kt_cross_entropy_fwd(void* logits, const void* targets, void* loss,
-                          int N, int V, float scale, long ignore_index,
-                          hipStream_t stream);
-void kt_scale_bf16(const void* in, void* out, const void* scale, long n,
-                   hipStream_t stream);
-void kt_adamw(void* p, const void* g, void* m, void* v, long n, float lr,
-              float beta1, float beta2, float eps, float wd, float bc1,
-              float bc2, float grad_scale, hipStream_t stream);
-void kt_attn_fwd(const void* q, const void* k, const void* v, void* o,
-                 void* lse, int B, int Hq, int Hkv, int S, float scale,
-                 hipStream_t stream);
-void kt_attn_fwd_ck(const void* q, const void* k, const void* v, void* o,
-                    void* lse, int B, int Hq, int Hkv, int S, float scale,
-                    const long* strides, hipStream_t stream);
-void kt_attn_fwd_ck_tr(const void* q, const void* k, const void* v, void* o,
-                       void* lse, int B, int Hq, int Hkv, int S, float scale,
-                       const long* strides, hipStream_t stream);
-void kt_attn_fwd_v3(const void* q, const void* k, const void* v, void* o,
-                    void* lse, int B, int Hq, int Hkv, int S, float scale,
-                    const long* strides, hipStream_t stream);
-void kt_pack_segments(const void* ptrs, const void* nbytes, const void* offs,
-                      void* base, int nseg, long max_nbytes, int to_base,
-                      hipStream_t stream);
-void kt_transpose_bf16(const void* src, long src_stride, void* dst, long R,
-                       long C, hipStream_t stream);
-void kt_transpose_segments_bf16(const void* src, void* dst, const void* table,
-                                int nseg, long max_tiles, hipStream_t stream);
-void kt_attn_bwd_ck(const void* q, const void* k, const void* v,
-                    const void* o, const void* do_, const void* lse, void* d,
-                    void* dq_acc, void* dq, void* dk, void* dv, int B, int Hq,
-                    int Hkv, int S, float scale, int mask_mode, int pipe,
-                    hipStream_t stream);
-void kt_paged_kv_write(const void* k_new, const void* v_new, void* k_pages,
-                       void* v_pages, const void* slot_mapping, long T,
-                       int Hkv, int hd, int page_size, long num_pages,
-                       long k_st, long k_sh, long v_st, long v_sh,
-                       hipStream_t stream);
-void kt_paged_kv_write_fp8(const void* k_new, const void* v_new,
-                           void* k_pages, void* v_pages,
-                           const void* slot_mapping, const void* k_inv,
-                           const void* v_inv, long T, int Hkv, int hd,
-                           int page_size, long num_pages, long k_st,
-                           long k_sh, long v_st, long v_sh,
-                           hipStream_t stream);
-int kt_paged_attention_decode(const void* q, const void* k_pages,
-                              const void* v_pages, const void* block_table,
-                              const void* seq_lens, void* out, void* po,
-                              void* pm, void* pl, int B, int Hq, int Hkv,
-                              int hd, int page_size, int num_pages,
-                              int max_blocks, int num_splits, float scale,
-                              int fp8, const void* k_scale,
-                              const void* v_scale, hipStream_t stream);
-int kt_paged_attention_prefill(const void* q, const void* k_pages,
-                               const void* v_pages, const void* block_table,
-                               const void* cu_q_lens, const void* seq_lens,
-                               void* out, long T, long q_st, long q_sh, int B,
-                               int Hq, int Hkv, int hd, int page_size,
-                               int num_pages, int max_blocks, int max_q_len,
-                               float scale, int fp8, const void* k_scale,
-                               const void* v_scale, hipStream_t stream);
-void kt_sample_tokens(const void* logits, long row_stride, int B, int V,
-                      const void* temperature, const void* top_k,
-                      const void* top_p, const void* seed, const void* offset,
-                      void* out, hipStream_t stream);
-void kt_token_logprobs(const void* logits, long row_stride, int B, int V,
-                       const void* token, const void* temperature, int top_n,
-                       void* logprob, void* rank, void* top_ids,
-                       void* top_logprobs, hipStream_t stream);
-int kt_linear_w8_plan(long N, long K);
-void kt_linear_w8(const void* x, long x_stride, const void* wq,
-                  const void* scale, void* y, void* part, int M, int N, int K,
-                  int S, hipStream_t stream);
-}
+#include "kt_launchers.h"
 
 namespace {
 
@@ -114,6 +23,16 @@ namespace {
 
 hipStream_t cur_stream(const at::Tensor& t) {
   return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
+}
+
+// t is an [n] contiguous GPU tensor of `dtype` on `device`; `what` is the
+// message: the argument's name and this requirement.
+void check_vec(const at::Tensor& t, at::ScalarType dtype, int64_t n,
+               const at::Device& device, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.device() == device &&
+                  t.scalar_type() == dtype && t.dim() == 1 &&
+                  t.size(0) == n && t.is_contiguous(),
+              what);
 }
 
 std::vector<at::Tensor> rmsnorm_fwd(const at::Tensor& x,
@@ -657,6 +576,24 @@ const void* scale_ptr(const c10::optional<at::Tensor>& s) {
   return s.has_value() ? s->data_ptr() : nullptr;
 }
 
+// q is [rows, Hq, hd] on the pools' device with the pools' head_dim and a
+// GQA group the paged kernels are instantiated for. `rows` names the leading
+// dim in the message. Returns (Hq, G).
+std::pair<int64_t, int64_t> check_paged_query(const at::Tensor& q,
+                                              const at::Tensor& k_pages,
+                                              const char* rows) {
+  const int64_t Hkv = k_pages.size(1);
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == k_pages.size(3), "q must be [",
+              rows, ", Hq, hd] with the pool's head_dim");
+  TORCH_CHECK(q.device() == k_pages.device(), "q and pools on one device");
+  const int64_t Hq = q.size(1);
+  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
+  const int64_t G = Hq / Hkv;
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8,
+              "group Hq/Hkv must be 1, 2, 4 or 8, got ", G);
+  return {Hq, G};
+}
+
 void paged_kv_write(const at::Tensor& k_new, const at::Tensor& v_new,
                     at::Tensor k_pages, at::Tensor v_pages,
                     const at::Tensor& slot_mapping,
@@ -684,27 +621,16 @@ void paged_kv_write(const at::Tensor& k_new, const at::Tensor& v_new,
                 "k_new/v_new rows must be 16-byte aligned");
   }
   const int64_t T = k_new.size(0);
-  TORCH_CHECK(slot_mapping.is_cuda() && slot_mapping.scalar_type() == at::kInt &&
-                  slot_mapping.is_contiguous() && slot_mapping.dim() == 1 &&
-                  slot_mapping.size(0) == T &&
-                  slot_mapping.device() == k_pages.device(),
-              "slot_mapping must be [T] contiguous int32 on the pool's device");
+  check_vec(slot_mapping, at::kInt, T, k_pages.device(),
+            "slot_mapping must be [T] contiguous int32 on the pool's device");
   if (T == 0) return;
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(k_pages.device());
-  if (fp8) {
-    kt_paged_kv_write_fp8(
-        k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(),
-        v_pages.data_ptr(), slot_mapping.data_ptr(), scale_ptr(k_inv_scale),
-        scale_ptr(v_inv_scale), (long)T, Hkv, hd, ps, (long)k_pages.size(0),
-        k_new.stride(0), k_new.stride(1), v_new.stride(0), v_new.stride(1),
-        cur_stream(k_pages));
-    return;
-  }
   kt_paged_kv_write(k_new.data_ptr(), v_new.data_ptr(), k_pages.data_ptr(),
-                    v_pages.data_ptr(), slot_mapping.data_ptr(), (long)T, Hkv,
-                    hd, ps, (long)k_pages.size(0), k_new.stride(0),
-                    k_new.stride(1), v_new.stride(0), v_new.stride(1),
-                    cur_stream(k_pages));
+                    v_pages.data_ptr(), slot_mapping.data_ptr(),
+                    scale_ptr(k_inv_scale), scale_ptr(v_inv_scale), (int)fp8,
+                    (long)T, Hkv, hd, ps, (long)k_pages.size(0),
+                    k_new.stride(0), k_new.stride(1), v_new.stride(0),
+                    v_new.stride(1), cur_stream(k_pages));
 }
 
 at::Tensor paged_attention_decode(const at::Tensor& q,
@@ -722,24 +648,16 @@ at::Tensor paged_attention_decode(const at::Tensor& q,
   const int64_t num_pages = k_pages.size(0);
   const int Hkv = (int)k_pages.size(1), ps = (int)k_pages.size(2);
   const int hd = (int)k_pages.size(3);
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == hd,
-              "q must be [B, Hq, hd] with the pool's head_dim");
-  TORCH_CHECK(q.device() == k_pages.device(), "q and pools on one device");
-  const int64_t B = q.size(0), Hq = q.size(1);
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
-  const int64_t G = Hq / Hkv;
-  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8,
-              "group Hq/Hkv must be 1, 2, 4 or 8, got ", G);
+  const auto [Hq, G] = check_paged_query(q, k_pages, "B");
+  const int64_t B = q.size(0);
   TORCH_CHECK(block_table.is_cuda() && block_table.scalar_type() == at::kInt &&
                   block_table.is_contiguous() && block_table.dim() == 2 &&
                   block_table.size(0) == B &&
                   block_table.device() == q.device(),
               "block_table must be [B, max_blocks] contiguous int32 on q's "
               "device");
-  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.scalar_type() == at::kInt &&
-                  seq_lens.is_contiguous() && seq_lens.dim() == 1 &&
-                  seq_lens.size(0) == B && seq_lens.device() == q.device(),
-              "seq_lens must be [B] contiguous int32 on q's device");
+  check_vec(seq_lens, at::kInt, B, q.device(),
+            "seq_lens must be [B] contiguous int32 on q's device");
   const int64_t max_blocks = block_table.size(1);
   // the kernel's token counters are int32 and step past the end by up to
   // one chunk (128 tokens) before the loop test
@@ -793,14 +711,8 @@ at::Tensor paged_attention_prefill(const at::Tensor& q,
   const int hd = (int)k_pages.size(3);
   TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16,
               "q must be bf16 on GPU");
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == hd,
-              "q must be [T, Hq, hd] with the pool's head_dim");
-  TORCH_CHECK(q.device() == k_pages.device(), "q and pools on one device");
-  const int64_t T = q.size(0), Hq = q.size(1);
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
-  const int64_t G = Hq / Hkv;
-  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8,
-              "group Hq/Hkv must be 1, 2, 4 or 8, got ", G);
+  const auto [Hq, G] = check_paged_query(q, k_pages, "T");
+  const int64_t T = q.size(0);
   if (q.numel() > 0) {
     TORCH_CHECK(q.stride(2) == 1, "q head dim must be contiguous");
     TORCH_CHECK(q.stride(0) % 8 == 0 && q.stride(1) % 8 == 0 &&
@@ -814,15 +726,10 @@ at::Tensor paged_attention_prefill(const at::Tensor& q,
               "block_table must be [B, max_blocks] contiguous int32 on q's "
               "device");
   const int64_t B = block_table.size(0);
-  TORCH_CHECK(cu_q_lens.is_cuda() && cu_q_lens.scalar_type() == at::kInt &&
-                  cu_q_lens.is_contiguous() && cu_q_lens.dim() == 1 &&
-                  cu_q_lens.size(0) == B + 1 &&
-                  cu_q_lens.device() == q.device(),
-              "cu_q_lens must be [B+1] contiguous int32 on q's device");
-  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.scalar_type() == at::kInt &&
-                  seq_lens.is_contiguous() && seq_lens.dim() == 1 &&
-                  seq_lens.size(0) == B && seq_lens.device() == q.device(),
-              "seq_lens must be [B] contiguous int32 on q's device");
+  check_vec(cu_q_lens, at::kInt, B + 1, q.device(),
+            "cu_q_lens must be [B+1] contiguous int32 on q's device");
+  check_vec(seq_lens, at::kInt, B, q.device(),
+            "seq_lens must be [B] contiguous int32 on q's device");
   const int64_t max_blocks = block_table.size(1);
   TORCH_CHECK(max_blocks * ps < (int64_t)INT32_MAX - 256,
               "max_blocks*page_size must fit int32");
@@ -847,14 +754,10 @@ at::Tensor paged_attention_prefill(const at::Tensor& q,
   return out;
 }
 
-at::Tensor sample_tokens(const at::Tensor& logits,
-                         const at::Tensor& temperature,
-                         const at::Tensor& top_k, const at::Tensor& top_p,
-                         const at::Tensor& seed, const at::Tensor& offset) {
-  // logits: [B, V] bf16, last dim contiguous, row base and stride 16 B
-  // aligned (ops.sample_tokens sends everything else to the reference).
-  // The five parameter vectors are [B] on the logits' device; their values
-  // are not looked at here (that would be a device sync).
+// logits: [B, V] bf16 on the GPU, V <= 262144, last dim contiguous, row base
+// and stride 16 B aligned. Returns (B, V, row stride in elements; 0 for one
+// row, whose stride is free).
+std::tuple<int64_t, int64_t, long> check_logits_rows(const at::Tensor& logits) {
   TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16 &&
                   logits.dim() == 2,
               "logits must be [B, V] bf16 on GPU");
@@ -867,26 +770,34 @@ at::Tensor sample_tokens(const at::Tensor& logits,
                   (B <= 1 ||
                    (logits.stride(0) >= 0 && logits.stride(0) % 8 == 0)),
               "logits rows must be 16-byte aligned");
-  const struct {
-    const at::Tensor* t;
-    at::ScalarType dt;
-    const char* name;
-  } params[] = {{&temperature, at::kFloat, "temperature must be [B] fp32"},
-                {&top_k, at::kInt, "top_k must be [B] int32"},
-                {&top_p, at::kFloat, "top_p must be [B] fp32"},
-                {&seed, at::kLong, "seed must be [B] int64"},
-                {&offset, at::kLong, "offset must be [B] int64"}};
-  for (const auto& p : params) {
-    TORCH_CHECK(p.t->is_cuda() && p.t->device() == logits.device() &&
-                    p.t->scalar_type() == p.dt && p.t->dim() == 1 &&
-                    p.t->size(0) == B && p.t->is_contiguous(),
-                p.name, ", contiguous, on the logits' device");
-  }
+  return {B, V, B > 1 ? (long)logits.stride(0) : 0};
+}
+
+at::Tensor sample_tokens(const at::Tensor& logits,
+                         const at::Tensor& temperature,
+                         const at::Tensor& top_k, const at::Tensor& top_p,
+                         const at::Tensor& seed, const at::Tensor& offset) {
+  // logits: [B, V] bf16, last dim contiguous, row base and stride 16 B
+  // aligned (ops.sample_tokens sends everything else to the reference).
+  // The five parameter vectors are [B] on the logits' device; their values
+  // are not looked at here (that would be a device sync).
+  const auto [B, V, row_stride] = check_logits_rows(logits);
+  const auto dev = logits.device();
+  check_vec(temperature, at::kFloat, B, dev,
+            "temperature must be [B] fp32, contiguous, on the logits' device");
+  check_vec(top_k, at::kInt, B, dev,
+            "top_k must be [B] int32, contiguous, on the logits' device");
+  check_vec(top_p, at::kFloat, B, dev,
+            "top_p must be [B] fp32, contiguous, on the logits' device");
+  check_vec(seed, at::kLong, B, dev,
+            "seed must be [B] int64, contiguous, on the logits' device");
+  check_vec(offset, at::kLong, B, dev,
+            "offset must be [B] int64, contiguous, on the logits' device");
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
   auto out = at::empty({B}, logits.options().dtype(at::kLong));
   if (B == 0) return out;
-  kt_sample_tokens(logits.data_ptr(), B > 1 ? (long)logits.stride(0) : 0,
-                   (int)B, (int)V, temperature.data_ptr(), top_k.data_ptr(),
+  kt_sample_tokens(logits.data_ptr(), row_stride, (int)B, (int)V,
+                   temperature.data_ptr(), top_k.data_ptr(),
                    top_p.data_ptr(), seed.data_ptr(), offset.data_ptr(),
                    out.data_ptr(), cur_stream(logits));
   return out;
@@ -900,31 +811,13 @@ std::vector<at::Tensor> token_logprobs(const at::Tensor& logits,
   // to the reference); token [B] int64 and temperature [B] fp32 on the
   // logits' device. Their values are not looked at here (that would be a
   // device sync): the kernel reads no logit for a token outside [0, V).
-  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16 &&
-                  logits.dim() == 2,
-              "logits must be [B, V] bf16 on GPU");
-  const int64_t B = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(V >= 1 && V <= 262144, "V must be in [1, 262144], got ", V);
-  TORCH_CHECK(B < (int64_t)INT32_MAX, "batch too large");
-  TORCH_CHECK(V == 1 || logits.stride(1) == 1,
-              "logits' last dim must be contiguous");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0 &&
-                  (B <= 1 ||
-                   (logits.stride(0) >= 0 && logits.stride(0) % 8 == 0)),
-              "logits rows must be 16-byte aligned");
+  const auto [B, V, row_stride] = check_logits_rows(logits);
   TORCH_CHECK(top_n >= 0 && top_n <= 32, "top_n must be in [0, 32], got ",
               top_n);
-  TORCH_CHECK(token.is_cuda() && token.device() == logits.device() &&
-                  token.scalar_type() == at::kLong && token.dim() == 1 &&
-                  token.size(0) == B && token.is_contiguous(),
-              "token must be [B] int64, contiguous, on the logits' device");
-  TORCH_CHECK(temperature.is_cuda() &&
-                  temperature.device() == logits.device() &&
-                  temperature.scalar_type() == at::kFloat &&
-                  temperature.dim() == 1 && temperature.size(0) == B &&
-                  temperature.is_contiguous(),
-              "temperature must be [B] fp32, contiguous, on the logits' "
-              "device");
+  check_vec(token, at::kLong, B, logits.device(),
+            "token must be [B] int64, contiguous, on the logits' device");
+  check_vec(temperature, at::kFloat, B, logits.device(),
+            "temperature must be [B] fp32, contiguous, on the logits' device");
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
   auto f32 = logits.options().dtype(at::kFloat);
   auto i32 = logits.options().dtype(at::kInt);
@@ -933,9 +826,9 @@ std::vector<at::Tensor> token_logprobs(const at::Tensor& logits,
   auto top_ids = at::empty({B, top_n}, i32);
   auto top_lp = at::empty({B, top_n}, f32);
   if (B > 0)
-    kt_token_logprobs(logits.data_ptr(), B > 1 ? (long)logits.stride(0) : 0,
-                      (int)B, (int)V, token.data_ptr(),
-                      temperature.data_ptr(), (int)top_n, logprob.data_ptr(),
+    kt_token_logprobs(logits.data_ptr(), row_stride, (int)B, (int)V,
+                      token.data_ptr(), temperature.data_ptr(), (int)top_n,
+                      logprob.data_ptr(),
                       rank.data_ptr(), top_ids.data_ptr(), top_lp.data_ptr(),
                       cur_stream(logits));
   return {logprob, rank, top_ids, top_lp};
@@ -957,10 +850,8 @@ at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq,
               "device");
   const int64_t M = x.size(0), K = x.size(1), N = wq.size(0);
   TORCH_CHECK(wq.size(1) == K, "x's last dim must be weight_q's K");
-  TORCH_CHECK(scale.is_cuda() && scale.device() == x.device() &&
-                  scale.scalar_type() == at::kFloat && scale.dim() == 1 &&
-                  scale.size(0) == N && scale.is_contiguous(),
-              "weight_scale must be [N] fp32, contiguous, on x's device");
+  check_vec(scale, at::kFloat, N, x.device(),
+            "weight_scale must be [N] fp32, contiguous, on x's device");
   TORCH_CHECK(M >= 1 && M <= 32, "M must be in [1, 32], got ", M);
   TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24),
               "K must be a multiple of 128 up to 2^24, got ", K);

@@ -15,24 +15,13 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
-typedef unsigned short u16;
-typedef ushort vec8u __attribute__((ext_vector_type(8)));
+#include "device_common.h"
+#include "kt_launchers.h"
+
 typedef ushort vec4u __attribute__((ext_vector_type(4)));
 typedef float vec4f __attribute__((ext_vector_type(4)));
 
 #define WAVE 64
-
-__device__ __forceinline__ float bf2f(u16 x) {
-  unsigned int u = ((unsigned int)x) << 16;
-  return __uint_as_float(u);
-}
-__device__ __forceinline__ u16 f2bf(float f) {
-  // round-to-nearest-even bf16 conversion
-  unsigned int u = __float_as_uint(f);
-  unsigned int rounding = 0x7fff + ((u >> 16) & 1);
-  u += rounding;
-  return (u16)(u >> 16);
-}
 
 // Block-wide sum; every thread returns the total. Reusable across
 // iterations (trailing barrier protects the LDS scratch).

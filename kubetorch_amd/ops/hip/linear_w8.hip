@@ -33,15 +33,12 @@
 // Safety: columns n >= N read row N-1 again and are not stored; an empty K
 // slice writes zeros. Every index that scales with N*K is 64-bit.
 //
-// No torch headers here; bindings.cpp declares the extern "C" launchers.
+// No torch headers here; kt_launchers.h declares the extern "C" launchers.
 
 #include <hip/hip_runtime.h>
 
-typedef unsigned short u16;
-typedef unsigned int vec4w __attribute__((ext_vector_type(4)));
-typedef float vec2f __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "device_common.h"
+#include "kt_launchers.h"
 
 #define LW_THREADS 256
 #define LW_BN 128                    // output columns per workgroup
@@ -52,18 +49,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
-// the exact bf16 of two e4m3 values: high halves of their fp32
-__device__ __forceinline__ unsigned bf16_pair(vec2f f) {
-  return (__float_as_uint(f[0]) >> 16) | (__float_as_uint(f[1]) & 0xffff0000u);
-}
-
 // 8 e4m3 bytes (two dwords) -> one bf16x8 MFMA fragment
 __device__ __forceinline__ bf16x8 frag_fp8(unsigned lo, unsigned hi) {
-  vec4w o;
-  o[0] = bf16_pair(__builtin_amdgcn_cvt_pk_f32_fp8(lo, false));
-  o[1] = bf16_pair(__builtin_amdgcn_cvt_pk_f32_fp8(lo, true));
-  o[2] = bf16_pair(__builtin_amdgcn_cvt_pk_f32_fp8(hi, false));
-  o[3] = bf16_pair(__builtin_amdgcn_cvt_pk_f32_fp8(hi, true));
+  const vec2w a = e4m3x4_to_bf16(lo), b = e4m3x4_to_bf16(hi);
+  const vec4w o = {a[0], a[1], b[0], b[1]};
   return __builtin_bit_cast(bf16x8, o);
 }
 

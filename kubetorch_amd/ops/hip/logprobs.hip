@@ -36,6 +36,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bf16_keys.h"
+#include "kt_launchers.h"
+
 namespace {
 
 constexpr int LP_THREADS = 1024;
@@ -43,51 +46,8 @@ constexpr int LP_WAVES = LP_THREADS / 64;
 constexpr int LP_MAX_TOP = 32;
 constexpr int HIST_COPIES = 32;
 constexpr int HIST_PITCH = 257;  // copies land on different banks
-constexpr unsigned KEY_NEG_INF = 0x007Fu;  // key of -inf (bits 0xFF80)
-constexpr unsigned KEY_POS_INF = 0xFF80u;  // key of +inf (bits 0x7F80)
 
 typedef unsigned long long u64;
-
-// bf16 bits -> 16-bit key with key order == value order. NaN counts as
-// -inf and -0 as +0, so equal keys are exactly equal logits. No key is 0.
-__device__ __forceinline__ unsigned key_of(unsigned bits) {
-  bits &= 0xFFFFu;
-  if ((bits & 0x7FFFu) > 0x7F80u) bits = 0xFF80u;
-  if (bits == 0x8000u) bits = 0u;
-  return (bits & 0x8000u) ? (~bits & 0xFFFFu) : (bits | 0x8000u);
-}
-
-__device__ __forceinline__ float value_of(unsigned key) {
-  const unsigned bits = (key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu);
-  return __uint_as_float(bits << 16);
-}
-
-// The 8 keys of vector v into k[0..7].
-__device__ __forceinline__ void load_keys(const uint16_t* row, int v,
-                                          unsigned* k) {
-  const uint4 q = reinterpret_cast<const uint4*>(row)[v];
-  const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    k[2 * j] = key_of(w[j]);
-    k[2 * j + 1] = key_of(w[j] >> 16);
-  }
-}
-
-// f(key) for every element of the row: 16-byte loads of 8 logits, then the
-// V % 8 tail one element per thread.
-template <typename F>
-__device__ __forceinline__ void for_each_key(const uint16_t* row, int V, F f) {
-  const int nvec = V >> 3;
-  for (int v = threadIdx.x; v < nvec; v += LP_THREADS) {
-    unsigned k[8];
-    load_keys(row, v, k);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f(k[j]);
-  }
-  const int t = nvec * 8 + (int)threadIdx.x;
-  if (t < V) f(key_of(row[t]));
-}
 
 // Maximum (is_max) or sum of v over the workgroup, to every thread.
 __device__ __forceinline__ unsigned block_reduce(unsigned v, bool is_max,
@@ -241,14 +201,14 @@ token_logprobs_kernel(const uint16_t* __restrict__ logits, long row_stride,
   unsigned kmax = 0, above = 0, ninf = 0;
   if (top_n > 0) {
     clear_hist(hist);
-    for_each_key(row, V, [&](unsigned key) {
+    for_each_key<LP_THREADS>(row, V, [&](int, unsigned key) {
       kmax = key > kmax ? key : kmax;
       above += key > ktok;
       ninf += key == KEY_POS_INF;
       hist_add(hist, key >> 8);
     });
   } else {
-    for_each_key(row, V, [&](unsigned key) {
+    for_each_key<LP_THREADS>(row, V, [&](int, unsigned key) {
       kmax = key > kmax ? key : kmax;
       above += key > ktok;
       ninf += key == KEY_POS_INF;
@@ -268,7 +228,7 @@ token_logprobs_kernel(const uint16_t* __restrict__ logits, long row_stride,
     // pass 2
     const float xmax = lp.xmax;
     double part = 0.0;
-    for_each_key(row, V, [&](unsigned key) {
+    for_each_key<LP_THREADS>(row, V, [&](int, unsigned key) {
       part += (double)expf((value_of(key) - xmax) / T);
     });
     lp.logS = log(block_sum_f64(part, red64));
@@ -289,7 +249,7 @@ token_logprobs_kernel(const uint16_t* __restrict__ logits, long row_stride,
   const unsigned hi = sel[0];
   const unsigned need_hi = sel[1];
   clear_hist(hist);
-  for_each_key(row, V, [&](unsigned key) {
+  for_each_key<LP_THREADS>(row, V, [&](int, unsigned key) {
     if ((key >> 8) == hi) hist_add(hist, key & 255u);
   });
   select_bin(hist, need_hi, bins, sel);

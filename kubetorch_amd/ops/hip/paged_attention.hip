@@ -28,58 +28,20 @@
 // everything past max_blocks*page_size are skipped: never loaded, never
 // multiplied by a zero probability.
 //
-// No torch headers here; bindings.cpp declares the extern "C" launchers.
+// No torch headers here; kt_launchers.h declares the extern "C" launchers.
+// Outputs are rounded with f2bf_nan: NaN from non-finite K/V data stays NaN.
 
 #include <hip/hip_runtime.h>
 
-typedef unsigned short u16;
-typedef ushort vec8u __attribute__((ext_vector_type(8)));
-typedef unsigned int vec2w __attribute__((ext_vector_type(2)));
-typedef float vec2f __attribute__((ext_vector_type(2)));
+#include "device_common.h"
+#include "kt_launchers.h"
+#include "paged_common.h"
 
 #define PA_WAVES 4
 #define PA_THREADS (PA_WAVES * 64)
 #define PA_UNROLL 4
 
 namespace {
-
-__device__ __forceinline__ float bf2f(u16 x) {
-  return __uint_as_float(((unsigned int)x) << 16);
-}
-__device__ __forceinline__ u16 f2bf(float f) {
-  // round-to-nearest-even; NaN (from non-finite K/V data) stays NaN
-  unsigned int u = __float_as_uint(f);
-  if (f != f) return (u16)0x7fc0;
-  u += 0x7fff + ((u >> 16) & 1);
-  return (u16)(u >> 16);
-}
-
-// The 8 K/V elements a lane loads at once: 16 B of bf16 or 8 B of e4m3.
-template <bool FP8>
-struct KV8 {
-  typedef u16 elem;
-  typedef vec8u vec;
-  static __device__ __forceinline__ void to_f32(vec v, float* f) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = bf2f(v[e]);
-  }
-};
-template <>
-struct KV8<true> {
-  typedef unsigned char elem;
-  typedef vec2w vec;
-  static __device__ __forceinline__ void to_f32(vec v, float* f) {
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-      const vec2f lo = __builtin_amdgcn_cvt_pk_f32_fp8(v[w], false);
-      const vec2f hi = __builtin_amdgcn_cvt_pk_f32_fp8(v[w], true);
-      f[4 * w] = lo[0];
-      f[4 * w + 1] = lo[1];
-      f[4 * w + 2] = hi[0];
-      f[4 * w + 3] = hi[1];
-    }
-  }
-};
 
 // fp32 -> the value the e4m3 conversion rounds: x * inv_scale clamped to
 // the finite range +-448 (so +-inf saturate). fmin/fmax drop a NaN operand,
@@ -103,6 +65,35 @@ __device__ __forceinline__ vec2w quantize8(vec8u x, float inv_scale) {
   }
   return r;
 }
+
+// The 8 K/V elements a lane loads at once: 16 B of bf16 or 8 B of e4m3;
+// `store` is the one place where the two page writes differ.
+template <bool FP8>
+struct KV8 {
+  typedef u16 elem;
+  typedef vec8u vec;
+  static __device__ __forceinline__ void to_f32(vec v, float* f) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = bf2f(v[e]);
+  }
+  // 8 bf16 into a pool row as they are
+  static __device__ __forceinline__ void store(elem* dst, vec8u x, float) {
+    *reinterpret_cast<vec8u*>(dst) = x;
+  }
+};
+template <>
+struct KV8<true> {
+  typedef unsigned char elem;
+  typedef vec2w vec;
+  static __device__ __forceinline__ void to_f32(vec v, float* f) {
+    e4m3x4_to_f32(v[0], f);
+    e4m3x4_to_f32(v[1], f + 4);
+  }
+  // 8 bf16 times the head's 1/scale into a pool row as 8 e4m3 bytes
+  static __device__ __forceinline__ void store(elem* dst, vec8u x, float inv) {
+    *reinterpret_cast<vec2w*>(dst) = quantize8(x, inv);
+  }
+};
 
 // Sum over the LPT (8 or 16) adjacent lanes that hold one token row; every
 // lane of the group gets the total. DPP controls: quad_perm [1,0,3,2],
@@ -132,44 +123,20 @@ __device__ __forceinline__ float merge_weight(float m, float M) {
 // ---------------------------------------------------------------------------
 // paged_kv_write
 // ---------------------------------------------------------------------------
-__global__ void paged_kv_write_kernel(const u16* __restrict__ k_new,
-                                      const u16* __restrict__ v_new,
-                                      u16* __restrict__ k_pages,
-                                      u16* __restrict__ v_pages,
-                                      const int* __restrict__ slot_mapping,
-                                      long total_vecs, int Hkv, int hd,
-                                      int page_size, long pool_tokens,
-                                      long k_st, long k_sh, long v_st,
-                                      long v_sh) {
-  const int vpr = hd >> 3;  // 16 B vectors per head row
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total_vecs;
-       i += (long)gridDim.x * blockDim.x) {
-    const int j = (int)(i % vpr);
-    const long th = i / vpr;
-    const int h = (int)(th % Hkv);
-    const long t = th / Hkv;
-    const long slot = slot_mapping[t];
-    if (slot < 0 || slot >= pool_tokens) continue;  // "write nothing"
-    const long page = slot / page_size;
-    const long off = slot - page * page_size;
-    const size_t dst = (((size_t)page * Hkv + h) * page_size + off) * hd + j * 8;
-    *reinterpret_cast<vec8u*>(k_pages + dst) =
-        *reinterpret_cast<const vec8u*>(k_new + t * k_st + h * k_sh + j * 8);
-    *reinterpret_cast<vec8u*>(v_pages + dst) =
-        *reinterpret_cast<const vec8u*>(v_new + t * v_st + h * v_sh + j * 8);
-  }
-}
-
-// The same scatter into fp8 pools: a lane loads 8 bf16 of K and of V,
-// multiplies by the head's 1/scale (computed on the host side of the op),
-// and stores 8 bytes of each.
-__global__ void paged_kv_write_fp8_kernel(
+// A lane loads 8 bf16 of K and of V (16 B each). bf16 pools take them as
+// they are; fp8 pools take each multiplied by the head's 1/scale (k_inv /
+// v_inv, computed on the host side of the op, not read otherwise) as 8 bytes.
+// k_inv / v_inv come last: the arguments both instantiations read share one
+// layout.
+template <bool FP8>
+__global__ void paged_kv_write_kernel(
     const u16* __restrict__ k_new, const u16* __restrict__ v_new,
-    unsigned char* __restrict__ k_pages, unsigned char* __restrict__ v_pages,
-    const int* __restrict__ slot_mapping, const float* __restrict__ k_inv,
-    const float* __restrict__ v_inv, long total_vecs, int Hkv, int hd,
+    typename KV8<FP8>::elem* __restrict__ k_pages,
+    typename KV8<FP8>::elem* __restrict__ v_pages,
+    const int* __restrict__ slot_mapping, long total_vecs, int Hkv, int hd,
     int page_size, long pool_tokens, long k_st, long k_sh, long v_st,
-    long v_sh) {
+    long v_sh, const float* __restrict__ k_inv,
+    const float* __restrict__ v_inv) {
   const int vpr = hd >> 3;  // 8-element vectors per head row
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total_vecs;
        i += (long)gridDim.x * blockDim.x) {
@@ -182,12 +149,14 @@ __global__ void paged_kv_write_fp8_kernel(
     const long page = slot / page_size;
     const long off = slot - page * page_size;
     const size_t dst = (((size_t)page * Hkv + h) * page_size + off) * hd + j * 8;
-    *reinterpret_cast<vec2w*>(k_pages + dst) = quantize8(
+    KV8<FP8>::store(
+        k_pages + dst,
         *reinterpret_cast<const vec8u*>(k_new + t * k_st + h * k_sh + j * 8),
-        k_inv[h]);
-    *reinterpret_cast<vec2w*>(v_pages + dst) = quantize8(
+        FP8 ? k_inv[h] : 1.f);
+    KV8<FP8>::store(
+        v_pages + dst,
         *reinterpret_cast<const vec8u*>(v_new + t * v_st + h * v_sh + j * 8),
-        v_inv[h]);
+        FP8 ? v_inv[h] : 1.f);
   }
 }
 
@@ -392,7 +361,7 @@ __global__ __launch_bounds__(PA_THREADS) void paged_attn_decode_kernel(
     const size_t hrow = (size_t)b * Hq + kvh * G + g;
     if (num_splits == 1) {
       // L == 0 only for an empty sequence: an all-zero row
-      out[hrow * HD + d] = L > 0.f ? f2bf(a / L) : (u16)0;
+      out[hrow * HD + d] = L > 0.f ? f2bf_nan(a / L) : (u16)0;
     } else {
       const size_t prow = hrow * num_splits + split;
       po[prow * HD + d] = a;
@@ -425,7 +394,7 @@ __global__ void paged_attn_combine_kernel(const float* __restrict__ po,
     a += po[(hrow * num_splits + s) * HD + d] * f;
     L += l[s] * f;
   }
-  out[hrow * HD + d] = L > 0.f ? f2bf(a / L) : (u16)0;
+  out[hrow * HD + d] = L > 0.f ? f2bf_nan(a / L) : (u16)0;
 }
 
 template <int HD, int G, bool FP8>
@@ -449,8 +418,11 @@ void launch_decode(const void* q, const void* k_pages, const void* v_pages,
 
 extern "C" {
 
+// bf16 k_new / v_new rows into the pools. fp8 != 0: e4m3 pools, and k_inv /
+// v_inv [Hkv] fp32 device arrays hold 1/scale per kv head.
 void kt_paged_kv_write(const void* k_new, const void* v_new, void* k_pages,
-                       void* v_pages, const void* slot_mapping, long T,
+                       void* v_pages, const void* slot_mapping,
+                       const void* k_inv, const void* v_inv, int fp8, long T,
                        int Hkv, int hd, int page_size, long num_pages,
                        long k_st, long k_sh, long v_st, long v_sh,
                        hipStream_t stream) {
@@ -458,32 +430,19 @@ void kt_paged_kv_write(const void* k_new, const void* v_new, void* k_pages,
   if (total == 0) return;
   long blocks = (total + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(paged_kv_write_kernel, dim3((unsigned)blocks), dim3(256),
-                     0, stream, (const u16*)k_new, (const u16*)v_new,
-                     (u16*)k_pages, (u16*)v_pages, (const int*)slot_mapping,
-                     total, Hkv, hd, page_size, num_pages * page_size, k_st,
-                     k_sh, v_st, v_sh);
-}
-
-// bf16 k_new / v_new rows into e4m3 pools; k_inv / v_inv [Hkv] fp32 device
-// arrays hold 1/scale per kv head.
-void kt_paged_kv_write_fp8(const void* k_new, const void* v_new,
-                           void* k_pages, void* v_pages,
-                           const void* slot_mapping, const void* k_inv,
-                           const void* v_inv, long T, int Hkv, int hd,
-                           int page_size, long num_pages, long k_st,
-                           long k_sh, long v_st, long v_sh,
-                           hipStream_t stream) {
-  const long total = T * Hkv * (hd / 8);
-  if (total == 0) return;
-  long blocks = (total + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(paged_kv_write_fp8_kernel, dim3((unsigned)blocks),
-                     dim3(256), 0, stream, (const u16*)k_new,
-                     (const u16*)v_new, (unsigned char*)k_pages,
-                     (unsigned char*)v_pages, (const int*)slot_mapping,
-                     (const float*)k_inv, (const float*)v_inv, total, Hkv, hd,
-                     page_size, num_pages * page_size, k_st, k_sh, v_st, v_sh);
+#define KT_KVW_LAUNCH(FP8_)                                                  \
+  hipLaunchKernelGGL(                                                        \
+      paged_kv_write_kernel<FP8_>, dim3((unsigned)blocks), dim3(256), 0,     \
+      stream, (const u16*)k_new, (const u16*)v_new,                          \
+      (KV8<FP8_>::elem*)k_pages, (KV8<FP8_>::elem*)v_pages,                  \
+      (const int*)slot_mapping, total, Hkv, hd, page_size,                   \
+      num_pages * page_size, k_st, k_sh, v_st, v_sh, (const float*)k_inv,    \
+      (const float*)v_inv)
+  if (fp8)
+    KT_KVW_LAUNCH(true);
+  else
+    KT_KVW_LAUNCH(false);
+#undef KT_KVW_LAUNCH
 }
 
 // Returns 0, or -1 for a configuration with no instantiation (the binding
@@ -499,8 +458,7 @@ int kt_paged_attention_decode(const void* q, const void* k_pages,
                               int fp8, const void* k_scale,
                               const void* v_scale, hipStream_t stream) {
   const int G = Hq / Hkv;
-  int page_shift = 0;
-  while ((1 << page_shift) < page_size) ++page_shift;
+  const int page_shift = paged_page_shift(page_size);
   const float qscale = scale * 1.4426950408889634f;
 #define KT_PA_LAUNCH(HD_, G_, FP8_)                                        \
   launch_decode<HD_, G_, FP8_>(                                            \
@@ -508,23 +466,7 @@ int kt_paged_attention_decode(const void* q, const void* k_pages,
       out, (float*)po, (float*)pm, (float*)pl, B, Hkv, num_pages,          \
       max_blocks, page_shift, num_splits, qscale, (const float*)k_scale,   \
       (const float*)v_scale, stream)
-#define KT_PA_CASE(HD_, G_)           \
-  if (hd == HD_ && G == G_) {         \
-    if (fp8)                          \
-      KT_PA_LAUNCH(HD_, G_, true);    \
-    else                              \
-      KT_PA_LAUNCH(HD_, G_, false);   \
-  } else
-  KT_PA_CASE(64, 1)
-  KT_PA_CASE(64, 2)
-  KT_PA_CASE(64, 4)
-  KT_PA_CASE(64, 8)
-  KT_PA_CASE(128, 1)
-  KT_PA_CASE(128, 2)
-  KT_PA_CASE(128, 4)
-  KT_PA_CASE(128, 8)
-  return -1;
-#undef KT_PA_CASE
+  KT_PAGED_DISPATCH(hd, G, fp8, KT_PA_LAUNCH);
 #undef KT_PA_LAUNCH
   if (num_splits > 1)
     hipLaunchKernelGGL(paged_attn_combine_kernel, dim3((unsigned)B * Hq),

@@ -39,17 +39,15 @@
 // tiles. k_scale folds into the score scale, v_scale into the epilogue's
 // 1/l.
 //
-// No torch headers here; bindings.cpp declares the extern "C" launcher.
+// No torch headers here; kt_launchers.h declares the extern "C" launcher.
 
 #include <hip/hip_runtime.h>
 
-typedef unsigned short u16;
-typedef ushort vec8u __attribute__((ext_vector_type(8)));
-typedef unsigned int vec4w __attribute__((ext_vector_type(4)));
-typedef float vec2f __attribute__((ext_vector_type(2)));
+#include "device_common.h"
+#include "kt_launchers.h"
+#include "paged_common.h"
+
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define PP_THREADS 256
 #define PP_MROWS 128  // M rows (query token x group head) per workgroup
@@ -76,20 +74,13 @@ struct Chunk<true> {
   typedef unsigned char elem;
   typedef vec4w vec;
   static constexpr int N = 16;
-  // e4m3 -> fp32 has at most 3 mantissa bits, so its high half is the
-  // exact bf16
-  static __device__ __forceinline__ unsigned bf16_pair(vec2f f) {
-    return (__float_as_uint(f[0]) >> 16) |
-           (__float_as_uint(f[1]) & 0xffff0000u);
-  }
   static __device__ __forceinline__ void to_lds(u16* dst, vec v) {
     vec4w o[2];
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
-      o[w >> 1][2 * (w & 1)] =
-          bf16_pair(__builtin_amdgcn_cvt_pk_f32_fp8(v[w], false));
-      o[w >> 1][2 * (w & 1) + 1] =
-          bf16_pair(__builtin_amdgcn_cvt_pk_f32_fp8(v[w], true));
+      const vec2w b = e4m3x4_to_bf16(v[w]);
+      o[w >> 1][2 * (w & 1)] = b[0];
+      o[w >> 1][2 * (w & 1) + 1] = b[1];
     }
     *reinterpret_cast<vec4w*>(dst) = o[0];
     *reinterpret_cast<vec4w*>(dst + 8) = o[1];
@@ -393,8 +384,7 @@ int kt_paged_attention_prefill(const void* q, const void* k_pages,
                                float scale, int fp8, const void* k_scale,
                                const void* v_scale, hipStream_t stream) {
   const int G = Hq / Hkv;
-  int page_shift = 0;
-  while ((1 << page_shift) < page_size) ++page_shift;
+  const int page_shift = paged_page_shift(page_size);
   const float qscale = scale * 1.4426950408889634f;
 #define KT_PP_LAUNCH(HD_, G_, FP8_)                                         \
   launch_prefill<HD_, G_, FP8_>(                                            \
@@ -402,25 +392,9 @@ int kt_paged_attention_prefill(const void* q, const void* k_pages,
       (const int*)seq_lens, out, T, q_st, q_sh, B, Hkv, num_pages,          \
       max_blocks, page_shift, max_q_len, qscale, (const float*)k_scale,     \
       (const float*)v_scale, stream)
-#define KT_PP_CASE(HD_, G_)           \
-  if (hd == HD_ && G == G_) {         \
-    if (fp8)                          \
-      KT_PP_LAUNCH(HD_, G_, true);    \
-    else                              \
-      KT_PP_LAUNCH(HD_, G_, false);   \
-    return 0;                         \
-  }
-  KT_PP_CASE(64, 1)
-  KT_PP_CASE(64, 2)
-  KT_PP_CASE(64, 4)
-  KT_PP_CASE(64, 8)
-  KT_PP_CASE(128, 1)
-  KT_PP_CASE(128, 2)
-  KT_PP_CASE(128, 4)
-  KT_PP_CASE(128, 8)
-#undef KT_PP_CASE
+  KT_PAGED_DISPATCH(hd, G, fp8, KT_PP_LAUNCH);
 #undef KT_PP_LAUNCH
-  return -1;
+  return 0;
 }
 
 }  // extern "C"

@@ -31,29 +31,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bf16_keys.h"
+#include "kt_launchers.h"
+
 namespace {
 
 constexpr int SAMPLER_THREADS = 1024;
 constexpr int SAMPLER_WAVES = SAMPLER_THREADS / 64;
-constexpr unsigned KEY_NEG_INF = 0x007Fu;  // key of -inf (bits 0xFF80)
-constexpr unsigned KEY_POS_INF = 0xFF80u;  // key of +inf (bits 0x7F80)
 constexpr float MASS_ONE = 17592186044416.f;  // 2^44: V <= 2^18 sums < 2^63
 
 typedef unsigned long long u64;
-
-// bf16 bits -> 16-bit key with key order == value order. NaN counts as
-// -inf and -0 as +0, so equal keys are exactly equal logits.
-__device__ __forceinline__ unsigned key_of(unsigned bits) {
-  bits &= 0xFFFFu;
-  if ((bits & 0x7FFFu) > 0x7F80u) bits = 0xFF80u;
-  if (bits == 0x8000u) bits = 0u;
-  return (bits & 0x8000u) ? (~bits & 0xFFFFu) : (bits | 0x8000u);
-}
-
-__device__ __forceinline__ float value_of(unsigned key) {
-  const unsigned bits = (key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu);
-  return __uint_as_float(bits << 16);
-}
 
 // fp32 (never NaN here) -> 32-bit key with key order == value order
 __device__ __forceinline__ unsigned score_key(float s) {
@@ -87,25 +74,6 @@ __device__ __forceinline__ u64 block_max64(u64 v, u64* red) {
 #pragma unroll
   for (int w = 1; w < SAMPLER_WAVES; ++w) r = red[w] > r ? red[w] : r;
   return r;
-}
-
-// f(index, key) for every element of the row: 16-byte loads of 8 logits,
-// then the V % 8 tail one element per thread.
-template <typename F>
-__device__ __forceinline__ void for_each_key(const uint16_t* row, int V, F f) {
-  const int nvec = V >> 3;
-  const uint4* rv = reinterpret_cast<const uint4*>(row);
-  for (int v = threadIdx.x; v < nvec; v += SAMPLER_THREADS) {
-    const uint4 q = rv[v];
-    const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f(v * 8 + 2 * j, key_of(w[j]));
-      f(v * 8 + 2 * j + 1, key_of(w[j] >> 16));
-    }
-  }
-  const int t = nvec * 8 + (int)threadIdx.x;
-  if (t < V) f(t, key_of(row[t]));
 }
 
 __device__ __forceinline__ void clear_hist(u64* hist) {
@@ -253,7 +221,7 @@ sample_tokens_kernel(const uint16_t* __restrict__ logits, long row_stride,
   // pass A: the maximum and its lowest index. ~index in the low word makes
   // the 64-bit maximum prefer the lowest index; the start value is index 0.
   u64 best = 0xFFFFFFFFull;
-  for_each_key(row, V, [&](int i, unsigned key) {
+  for_each_key<SAMPLER_THREADS>(row, V, [&](int i, unsigned key) {
     const u64 c = ((u64)key << 32) | (unsigned)~i;
     best = c > best ? c : best;
   });
@@ -268,14 +236,14 @@ sample_tokens_kernel(const uint16_t* __restrict__ logits, long row_stride,
     unsigned kept = 0;  // tokens with key >= kept survive the filters
     if (k > 0 && k < V) {
       clear_hist(hist);
-      for_each_key(row, V, [&](int, unsigned key) {
+      for_each_key<SAMPLER_THREADS>(row, V, [&](int, unsigned key) {
         atomicAdd(&hist[key >> 8], 1ull);
       });
       select_bin(hist, false, (u64)k, 0, 0.0, sel);
       const unsigned hi = (unsigned)sel[0];
       const u64 need = sel[1];
       clear_hist(hist);
-      for_each_key(row, V, [&](int, unsigned key) {
+      for_each_key<SAMPLER_THREADS>(row, V, [&](int, unsigned key) {
         if ((key >> 8) == hi) atomicAdd(&hist[key & 255u], 1ull);
       });
       select_bin(hist, false, need, 0, 0.0, sel);
@@ -285,7 +253,7 @@ sample_tokens_kernel(const uint16_t* __restrict__ logits, long row_stride,
       const float xmax = value_of(kmax);
       const unsigned kk = kept;
       clear_hist(hist);
-      for_each_key(row, V, [&](int, unsigned key) {
+      for_each_key<SAMPLER_THREADS>(row, V, [&](int, unsigned key) {
         if (key >= kk && key > KEY_NEG_INF) {
           const float w = expf((value_of(key) - xmax) / T);
           atomicAdd(&hist[key >> 8], (u64)(w * MASS_ONE));
@@ -299,7 +267,7 @@ sample_tokens_kernel(const uint16_t* __restrict__ logits, long row_stride,
         const unsigned hi = (unsigned)sel[0];
         const u64 base = sel[1];
         clear_hist(hist);
-        for_each_key(row, V, [&](int, unsigned key) {
+        for_each_key<SAMPLER_THREADS>(row, V, [&](int, unsigned key) {
           if (key >= kk && (key >> 8) == hi && key > KEY_NEG_INF) {
             const float w = expf((value_of(key) - xmax) / T);
             atomicAdd(&hist[key & 255u], (u64)(w * MASS_ONE));
@@ -320,17 +288,12 @@ sample_tokens_kernel(const uint16_t* __restrict__ logits, long row_stride,
     float seen = -INFINITY;  // this thread's best score so far
     const float invT = 1.f / T;
     const int nvec = V >> 3;
-    const uint4* rv = reinterpret_cast<const uint4*>(row);
     for (int v = threadIdx.x; v < nvec; v += SAMPLER_THREADS) {
-      const uint4 q = rv[v];
-      const unsigned w[4] = {q.x, q.y, q.z, q.w};
+      unsigned k8[8];
+      load_keys(row, v, k8);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {  // four tokens share one Philox block
-        unsigned key[4];
-        key[0] = key_of(w[2 * h]);
-        key[1] = key_of(w[2 * h] >> 16);
-        key[2] = key_of(w[2 * h + 1]);
-        key[3] = key_of(w[2 * h + 1] >> 16);
+        const unsigned* key = k8 + 4 * h;
         if (key[0] < kept && key[1] < kept && key[2] < kept && key[3] < kept)
           continue;
         const Philox r = philox4x32_10((unsigned)(v * 2 + h), o0, o1, 0, k0, k1);

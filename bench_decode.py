@@ -32,6 +32,10 @@ sampler call, one more host copy per step).
 --weight-dtype fp8 quantises the model's linear weights in place after it is
 built (models.quantize_weights_fp8: e4m3 bytes, the skinny-M decode kernel);
 every other flag combines with it.
+--moe ExK converts the built dense model to a mixture of E experts, top K
+(models.convert_to_moe: MoEMLP, eager decode); --moe-fused then fuses it
+(models.fuse_moe: the routed-GEMM decode kernels, captured decode graph up to
+--batch 32).
 """
 import argparse
 import json
@@ -138,6 +142,10 @@ def main():
                     help="fused: one ops.sample_tokens call per step")
     ap.add_argument("--weight-dtype", default="bf16", choices=["bf16", "fp8"],
                     help="fp8: e4m3 weight-only linears (W8A16)")
+    ap.add_argument("--moe", default=None, metavar="ExK",
+                    help="convert to E experts, top K (e.g. 8x2)")
+    ap.add_argument("--moe-fused", action="store_true",
+                    help="fuse the MoE layers (needs --moe)")
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--top-k", type=int, default=0,
                     help="needs --sampler fused")
@@ -156,6 +164,13 @@ def main():
         ap.error("--shared-prefix must be in [0, --prompt]")
     if args.kv_dtype == "fp8" and args.kv != "paged":
         ap.error("--kv-dtype fp8 needs --kv paged")
+    if args.moe_fused and args.moe is None:
+        ap.error("--moe-fused needs --moe ExK")
+    if args.moe is not None:
+        try:
+            n_experts, top_k = (int(v) for v in args.moe.split("x"))
+        except ValueError:
+            ap.error("--moe takes ExK, e.g. 8x2")
 
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model, cfg = build_model(args.model, dev)
@@ -163,6 +178,14 @@ def main():
         from kubetorch_amd.models import quantize_weights_fp8
 
         model = quantize_weights_fp8(model, inplace=True)
+    if args.moe is not None:
+        from kubetorch_amd.models import convert_to_moe, fuse_moe
+
+        p = next(model.parameters())
+        model = convert_to_moe(model, n_experts=n_experts, top_k=top_k)
+        model = model.to(p.device, p.dtype).eval()
+        if args.moe_fused:
+            model = fuse_moe(model, inplace=True)
     run = (model, cfg, args.batch, args.prompt, args.new)
     mode = dict(kv=args.kv, page_size=args.page_size,
                 num_splits=args.num_splits)
@@ -205,6 +228,8 @@ def main():
         more["kv_dtype"] = "fp8"
     if args.weight_dtype == "fp8":
         more["weight_dtype"] = "fp8"
+    if args.moe is not None:
+        more.update(moe=args.moe, moe_fused=args.moe_fused)
     if args.sampler != "torch" or "sampling" in extra:
         more.update(sampler=args.sampler, temperature=args.temperature,
                     top_k=args.top_k, top_p=args.top_p)

@@ -7,7 +7,12 @@ from kubetorch_amd.models.llama import (  # noqa: F401
     llama3_70b,
     llama_tiny,
 )
-from kubetorch_amd.models.moe import MoEMLP, convert_to_moe  # noqa: F401
+from kubetorch_amd.models.moe import (  # noqa: F401
+    FusedMoEMLP,
+    MoEMLP,
+    convert_to_moe,
+    fuse_moe,
+)
 from kubetorch_amd.models.paged_kv import (  # noqa: F401
     PagedKVCache,
     calibrate_kv_scales,

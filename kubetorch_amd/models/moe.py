@@ -14,10 +14,18 @@ FFN uses the same fused SwiGLU op as the dense MLP. Two placements:
     traffic when top_k << n_experts/world) is a round-2 swap kept behind
     the same interface.
 
+FusedMoEMLP / fuse_moe are the single-rank inference form of the same
+block: the experts' weights stacked into two parameters and the whole MLP
+one ops.moe_mlp call, which at decode sizes (at most 32 tokens) runs the
+gfx950 routed-GEMM kernels without a host sync, so the serving engine keeps
+its captured decode graph.
+
 The reference ships no model code — this extends the
 flagship family the launchers run, and is the EP workload the SPMD
 launcher's process groups exist for.
 """
+import copy
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -139,4 +147,79 @@ def convert_to_moe(model, n_experts=8, top_k=2, ep_group=None, seed=0):
             _init_linear(ex.w_down, std,
                          seed * 100003 + li * 1009 + gid * 2 + 8)
         layer.mlp = moe.to(device=p.device, dtype=p.dtype)
+    return model
+
+
+class FusedMoEMLP(nn.Module):
+    """Inference form of a single-rank MoEMLP: `router` and the experts'
+    weights stacked as w_gate_up [E, 2I, D] and w_down [E, D, I]; forward is
+    the router followed by ops.moe_mlp.
+
+    A numerical contract of its own, not bit-equal to MoEMLP: the routing
+    weights stay fp32, the top-k sum is carried in fp32 and rounded once, and
+    h = silu(gate) * up is rounded once from fp32 (MoEMLP rounds the routing
+    weights, gate/up, each expert's output and every partial sum to the
+    model's dtype). Equal router logits go to the lowest expert index."""
+
+    # Calls of more rows than this run ops.moe_mlp's composition, which syncs
+    # the host: the serving engine captures no decode graph above it.
+    graph_max_rows = ops.MOE_MAX_ROWS
+
+    def __init__(self, dim, intermediate, n_experts=8, top_k=2, device=None,
+                 dtype=None):
+        super().__init__()
+        if not 1 <= top_k <= n_experts:
+            raise ValueError("top_k must be in [1, n_experts]")
+        self.dim = dim
+        self.intermediate = intermediate
+        self.n_experts = n_experts
+        self.top_k = top_k
+        kw = dict(device=device, dtype=dtype)
+        self.router = nn.Linear(dim, n_experts, bias=False, **kw)
+        self.w_gate_up = nn.Parameter(
+            torch.zeros(n_experts, 2 * intermediate, dim, **kw))
+        self.w_down = nn.Parameter(
+            torch.zeros(n_experts, dim, intermediate, **kw))
+
+    @classmethod
+    @torch.no_grad()
+    def from_moe(cls, moe):
+        """The fused module that holds a single-rank MoEMLP's weights."""
+        if getattr(moe, "ep_world", 1) > 1:
+            raise ValueError("FusedMoEMLP is single-rank: the MoEMLP is "
+                             f"sharded over {moe.ep_world} ranks")
+        w = moe.router.weight
+        inter = moe.experts[0].w_down.weight.shape[1]
+        new = cls(moe.dim, inter, moe.n_experts, moe.top_k, device="meta")
+        new.router.weight = nn.Parameter(w.detach().clone())
+        new.w_gate_up = nn.Parameter(torch.stack(
+            [ex.w_gate_up.weight.detach() for ex in moe.experts]))
+        new.w_down = nn.Parameter(torch.stack(
+            [ex.w_down.weight.detach() for ex in moe.experts]))
+        return new
+
+    def forward(self, x):
+        return ops.moe_mlp(x, self.router(x), self.w_gate_up, self.w_down,
+                           self.top_k)
+
+    def extra_repr(self):
+        return (f"dim={self.dim}, intermediate={self.intermediate}, "
+                f"n_experts={self.n_experts}, top_k={self.top_k}")
+
+
+def fuse_moe(model, inplace=False):
+    """Replace every MoEMLP of `model` with a FusedMoEMLP holding the same
+    weights (inference only). inplace=False works on a deep copy and leaves
+    `model` as it is. A model sharded by expert parallelism (ep_world > 1)
+    raises ValueError. Returns the fused model."""
+    from kubetorch_amd.models.quantize import _swap
+
+    for m in model.modules():
+        if isinstance(m, MoEMLP) and m.ep_world > 1:
+            raise ValueError("fuse_moe needs a single-rank model: a MoEMLP "
+                             f"is sharded over {m.ep_world} ranks")
+    if not inplace:
+        model = copy.deepcopy(model)
+    _swap(model, lambda m: isinstance(m, MoEMLP),
+          lambda name, m: FusedMoEMLP.from_moe(m))
     return model

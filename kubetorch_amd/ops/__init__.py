@@ -1697,6 +1697,175 @@ class LinearW8(torch.nn.Module):
 
 
 # ---------------------------------------------------------------------------
+# Routed expert MLP for decode (mixture of experts, top-k)
+# ---------------------------------------------------------------------------
+MOE_MAX_ROWS = 32          # the kernel's T; more tokens run the composition
+MOE_MAX_EXPERTS = 64
+MOE_MAX_TOP_K = 8
+MOE_DIM_MULTIPLE = 128
+MOE_MAX_DIM = 1 << 16
+
+
+def _check_moe_route(router_logits, top_k):
+    if not torch.is_tensor(router_logits) \
+            or not router_logits.is_floating_point() \
+            or router_logits.dtype in _FLOAT8_DTYPES:
+        raise ValueError("router_logits must be a floating-point tensor")
+    if router_logits.dim() < 1 or router_logits.shape[-1] < 1:
+        raise ValueError("router_logits must be [..., E] with E >= 1")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) \
+            or not 1 <= top_k <= router_logits.shape[-1]:
+        raise ValueError(f"top_k must be an int in [1, E], got {top_k!r}")
+
+
+def _moe_route_kernel_ok(logits2, top_k):
+    T, E = logits2.shape
+    return (logits2.is_cuda
+            and logits2.dtype in (torch.bfloat16, torch.float32)
+            and 1 <= T <= MOE_MAX_ROWS and E <= MOE_MAX_EXPERTS
+            and top_k <= MOE_MAX_TOP_K)
+
+
+def _moe_route_ref(logits2, top_k):
+    """The routing rule in torch: a stable descending sort with NaN as -inf;
+    the softmax of the k best in float64, rounded to fp32."""
+    v = torch.where(logits2.isnan(), float("-inf"), logits2)
+    vals, idx = torch.sort(v, dim=-1, descending=True, stable=True)
+    vals = vals[:, :top_k].double()
+    top = vals[:, :1]
+    ex = torch.where(vals == top, 0.0, vals - top).exp()  # inf - inf is 0
+    return idx[:, :top_k].int(), (ex / ex.sum(-1, keepdim=True)).float()
+
+
+def moe_route(router_logits, top_k):
+    """Top-k routing of router_logits [..., E] -> (sel [..., k] int32,
+    weights [..., k] fp32). sel lists a token's k largest logits in
+    descending order, equal logits lowest index first, NaN counting as -inf;
+    weights is the softmax over those k logits, exp(l_j - l_0) / sum with
+    l_j - l_0 = 0 where l_j == l_0 (so rows of equal infinities are uniform,
+    never NaN).
+
+    bf16 or fp32 logits on the GPU with at most 32 rows, E <= 64 and
+    top_k <= 8 run the gfx950 kernel (one workgroup, fp32, no host sync);
+    anything else, the CPU included, runs the torch composition."""
+    _check_moe_route(router_logits, top_k)
+    E = router_logits.shape[-1]
+    lead = router_logits.shape[:-1]
+    l2 = router_logits.reshape(-1, E)
+    if _moe_route_kernel_ok(l2, top_k):
+        sel, w = _ext().moe_route(l2.contiguous(), top_k)[:2]
+    else:
+        sel, w = _moe_route_ref(l2, top_k)
+    return sel.view(*lead, top_k), w.view(*lead, top_k)
+
+
+def _moe_kernel_ok(x, router_logits, w_gate_up, w_down, top_k):
+    """What the kernels take; everything else runs the composition."""
+    E, D, I = w_down.shape
+    if not (x.is_cuda and x.dtype == torch.bfloat16
+            and w_gate_up.dtype == torch.bfloat16
+            and w_down.dtype == torch.bfloat16
+            and router_logits.dtype in (torch.bfloat16, torch.float32)
+            and E <= MOE_MAX_EXPERTS and top_k <= MOE_MAX_TOP_K
+            and D % MOE_DIM_MULTIPLE == 0 and I % MOE_DIM_MULTIPLE == 0
+            and 0 < D <= MOE_MAX_DIM and 0 < I <= MOE_MAX_DIM
+            and w_gate_up.is_contiguous() and w_down.is_contiguous()):
+        return False
+    x2 = _w8_rows(x, D)
+    if x2 is None:
+        return False
+    T = x2.shape[0]
+    return (1 <= T <= MOE_MAX_ROWS and x2.stride(1) == 1
+            and x2.data_ptr() % 16 == 0
+            and (T == 1 or (0 <= x2.stride(0) <= 1 << 24
+                            and x2.stride(0) % 8 == 0)))
+
+
+def _moe_mlp_ref(x2, logits2, w_gate_up, w_down, top_k):
+    """The composition: route, then per picked expert gather its tokens, run
+    gate/up, SwiGLU and down, and add the weighted rows. bf16 and fp16 inputs
+    compute in fp32 with h rounded once to x's dtype, as the kernel does. The
+    nonzero() syncs the host."""
+    I = w_down.shape[2]
+    ct = torch.float64 if x2.dtype == torch.float64 else torch.float32
+    sel, weights = _moe_route_ref(logits2, top_k)
+    out = torch.zeros(x2.shape, dtype=ct, device=x2.device)
+    for e in sel.unique().tolist():
+        tok, kth = (sel == e).nonzero(as_tuple=True)
+        gu = torch.nn.functional.linear(x2[tok].to(ct), w_gate_up[e].to(ct))
+        h = (torch.nn.functional.silu(gu[:, :I]) * gu[:, I:]).to(x2.dtype)
+        y = torch.nn.functional.linear(h.to(ct), w_down[e].to(ct))
+        out.index_add_(0, tok, y * weights[tok, kth].to(ct).unsqueeze(-1))
+    return out.to(x2.dtype)
+
+
+def moe_down_splits(dim, intermediate, n_experts, top_k):
+    """The split-K factor moe_mlp's down GEMM chooses: a function of the
+    shapes alone, never of the number of tokens or of device data."""
+    return int(_ext().moe_down_splits(dim, intermediate, n_experts, top_k))
+
+
+def moe_mlp(x, router_logits, w_gate_up, w_down, top_k, num_splits=None):
+    """Top-k mixture of SwiGLU experts for inference:
+
+        out[t] = round(sum_j weights[t, j] * (h[t, j] @ w_down[e].T)),
+        h[t, j] = round(silu(x[t] @ Wg[e].T) * (x[t] @ Wu[e].T)),
+        e = sel[t, j],  (sel, weights) = moe_route(router_logits, top_k)
+
+    with Wg = w_gate_up[e, :I], Wu = w_gate_up[e, I:], fp32 accumulation in
+    an order the implementation chooses, fp32 routing weights, h rounded once
+    to x's dtype and the top-k sum rounded once. x is [..., D], router_logits
+    [..., E] with the same leading dimensions, w_gate_up [E, 2I, D] and
+    w_down [E, D, I] in x's dtype. Inference-only: x must not require grad
+    while grad is enabled.
+
+    bf16 GPU x with 1 <= T <= 32 rows, E <= 64, top_k <= 8, D and I multiples
+    of 128, contiguous weights, bf16 or fp32 logits and 16-byte aligned rows
+    runs the gfx950 kernels: four launches, no host sync (capturable in a
+    graph), only the picked experts' weights are read, bit-identical run to
+    run, a token's result independent of the other tokens in the call. Any
+    other valid input, the CPU included, runs a torch composition that loops
+    over the picked experts and syncs the host. num_splits overrides the
+    down GEMM's split-K factor (tests); the composition ignores it."""
+    for name, w in (("w_gate_up", w_gate_up), ("w_down", w_down)):
+        if not torch.is_tensor(w) or w.dim() != 3 \
+                or not w.is_floating_point() or w.dtype in _FLOAT8_DTYPES:
+            raise ValueError(f"{name} must be a 3-D floating-point tensor")
+    E, D, I = w_down.shape
+    if tuple(w_gate_up.shape) != (E, 2 * I, D):
+        raise ValueError(f"w_gate_up must be [{E}, {2 * I}, {D}] for w_down "
+                         f"{tuple(w_down.shape)}, got {tuple(w_gate_up.shape)}")
+    if not torch.is_tensor(x) or x.dim() < 1 or x.shape[-1] != D:
+        raise ValueError(f"x must be a tensor [..., {D}]")
+    if not (x.dtype == w_gate_up.dtype == w_down.dtype):
+        raise ValueError("x, w_gate_up and w_down must have one dtype, got "
+                         f"{x.dtype}, {w_gate_up.dtype}, {w_down.dtype}")
+    _check_moe_route(router_logits, top_k)
+    if tuple(router_logits.shape) != (*x.shape[:-1], E):
+        raise ValueError(f"router_logits must be {(*x.shape[:-1], E)}, got "
+                         f"{tuple(router_logits.shape)}")
+    if not (x.device == router_logits.device == w_gate_up.device
+            == w_down.device):
+        raise ValueError("x, router_logits and the weights must be on one "
+                         "device")
+    if num_splits is not None and not 1 <= int(num_splits) <= 64:
+        raise ValueError("num_splits must be in [1, 64]")
+    if torch.is_grad_enabled() and x.requires_grad:
+        raise RuntimeError("moe_mlp is inference-only: x requires grad")
+    w_gate_up, w_down = w_gate_up.detach(), w_down.detach()
+    if x.numel() == 0:
+        return torch.empty_like(x)
+    if _moe_kernel_ok(x, router_logits, w_gate_up, w_down, top_k):
+        out = _ext().moe_mlp(_w8_rows(x, D),
+                             router_logits.reshape(-1, E).contiguous(),
+                             w_gate_up, w_down, top_k, int(num_splits or 0))
+    else:
+        out = _moe_mlp_ref(x.reshape(-1, D), router_logits.reshape(-1, E),
+                           w_gate_up, w_down, top_k)
+    return out.view(x.shape)
+
+
+# ---------------------------------------------------------------------------
 # Fused AdamW on flat bf16 buckets (used by kubetorch_amd.parallel)
 # ---------------------------------------------------------------------------
 def adamw_(p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):

@@ -879,6 +879,87 @@ int64_t linear_w8_splits(int64_t N, int64_t K) {
   return kt_linear_w8_plan(N, K);
 }
 
+// (sel, weights, expert_count, expert_rows) of router logits [T, E]
+std::vector<at::Tensor> moe_route(const at::Tensor& logits, int64_t top_k) {
+  // logits: [T, E] bf16 or fp32, contiguous, 1 <= T <= 32, E <= 64,
+  // 1 <= top_k <= min(E, 8) (ops.moe_route sends everything else to the
+  // composition). The values are not looked at here.
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 &&
+                  logits.is_contiguous() &&
+                  (logits.scalar_type() == at::kBFloat16 ||
+                   logits.scalar_type() == at::kFloat),
+              "router_logits must be [T, E] bf16 or fp32, contiguous, on GPU");
+  const int64_t T = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(T >= 1 && T <= 32, "T must be in [1, 32], got ", T);
+  TORCH_CHECK(E >= 1 && E <= 64, "E must be in [1, 64], got ", E);
+  TORCH_CHECK(top_k >= 1 && top_k <= E && top_k <= 8,
+              "top_k must be in [1, min(E, 8)], got ", top_k);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(logits.device());
+  auto i32 = logits.options().dtype(at::kInt);
+  auto sel = at::empty({T, top_k}, i32);
+  auto weights = at::empty({T, top_k}, logits.options().dtype(at::kFloat));
+  auto count = at::empty({E}, i32);
+  auto rows = at::empty({E, 32}, i32);
+  kt_moe_route(logits.data_ptr(), logits.scalar_type() == at::kBFloat16,
+               sel.data_ptr(), weights.data_ptr(), count.data_ptr(),
+               rows.data_ptr(), (int)T, (int)E, (int)top_k,
+               cur_stream(logits));
+  return {sel, weights, count, rows};
+}
+
+at::Tensor moe_mlp(const at::Tensor& x, const at::Tensor& logits,
+                   const at::Tensor& w_gate_up, const at::Tensor& w_down,
+                   int64_t top_k, int64_t num_splits) {
+  // x: [T, D] bf16, last dim contiguous, row base and stride 16 B aligned;
+  // w_gate_up: [E, 2I, D] and w_down: [E, D, I] bf16 contiguous, D and I
+  // multiples of 128 up to 2^16 (ops.moe_mlp sends everything else to the
+  // composition). num_splits 0 is the kernel's own choice from the shapes.
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
+              "x must be [T, D] bf16 on GPU");
+  const int64_t T = x.size(0), D = x.size(1);
+  for (const at::Tensor* w : {&w_gate_up, &w_down})
+    TORCH_CHECK(w->is_cuda() && w->device() == x.device() &&
+                    w->scalar_type() == at::kBFloat16 && w->dim() == 3 &&
+                    w->is_contiguous(),
+                "expert weights must be 3-D bf16, contiguous, on x's device");
+  const int64_t E = w_gate_up.size(0), I = w_down.size(2);
+  TORCH_CHECK(w_gate_up.size(1) == 2 * I && w_gate_up.size(2) == D &&
+                  w_down.size(0) == E && w_down.size(1) == D,
+              "expected w_gate_up [E, 2I, D] and w_down [E, D, I]");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) == T &&
+                  logits.size(1) == E && logits.device() == x.device(),
+              "router_logits must be [T, E] on x's device");
+  TORCH_CHECK(D >= 128 && D % 128 == 0 && D <= (1 << 16) && I >= 128 &&
+                  I % 128 == 0 && I <= (1 << 16),
+              "D and I must be multiples of 128 up to 2^16, got ", D, ", ", I);
+  const int64_t xs = T > 1 ? x.stride(0) : D;
+  TORCH_CHECK(x.stride(1) == 1, "x's last dim must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  xs >= 0 && xs % 8 == 0 && xs <= (1 << 24),
+              "x rows must be 16-byte aligned, with a stride up to 2^24");
+  TORCH_CHECK(num_splits >= 0 && num_splits <= 64,
+              "num_splits must be in [0, 64], got ", num_splits);
+  const auto route = moe_route(logits, top_k);  // checks T, E and top_k
+  const int S = num_splits > 0 ? (int)num_splits
+                               : kt_moe_down_plan(D, I, (int)E, (int)top_k);
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  auto h = at::empty({T, top_k, I}, x.options());
+  auto part = at::empty({S, T, top_k, D}, x.options().dtype(at::kFloat));
+  auto out = at::empty({T, D}, x.options());
+  kt_moe_mlp(x.data_ptr(), (long)xs, w_gate_up.data_ptr(), w_down.data_ptr(),
+             route[1].data_ptr(), route[2].data_ptr(), route[3].data_ptr(),
+             h.data_ptr(), part.data_ptr(), out.data_ptr(), (int)T, (int)D,
+             (int)I, (int)E, (int)top_k, S, cur_stream(x));
+  return out;
+}
+
+int64_t moe_down_splits(int64_t D, int64_t I, int64_t E, int64_t top_k) {
+  TORCH_CHECK(D >= 128 && D % 128 == 0 && I >= 128 && I % 128 == 0 &&
+                  E >= 1 && top_k >= 1 && top_k <= E,
+              "bad (D, I, E, top_k)");
+  return kt_moe_down_plan(D, I, (int)E, (int)top_k);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -932,4 +1013,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "y = x @ (e4m3 weight * scale)^T for M <= 32 rows of bf16 x");
   mod.def("linear_w8_splits", &linear_w8_splits,
           "The split-K factor linear_w8 chooses for an [N, K] weight");
+  mod.def("moe_route", &moe_route,
+          "Top-k routing of [T, E] logits -> (sel, weights, count, rows)");
+  mod.def("moe_mlp", &moe_mlp,
+          "Routed expert SwiGLU MLP of T <= 32 rows of bf16 x -> [T, D]");
+  mod.def("moe_down_splits", &moe_down_splits,
+          "The split-K factor moe_mlp's down GEMM chooses for the shapes");
 }

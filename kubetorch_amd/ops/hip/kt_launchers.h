@@ -114,4 +114,15 @@ void kt_linear_w8(const void* x, long x_stride, const void* wq,
                   const void* scale, void* y, void* part, int M, int N, int K,
                   int S, hipStream_t stream);
 
+// moe.hip. kt_moe_route writes the routing table that kt_moe_mlp reads.
+int kt_moe_down_plan(long D, long I, int E, int top_k);
+void kt_moe_route(const void* logits, int is_bf16, void* sel, void* weights,
+                  void* expert_count, void* expert_rows, int T, int E,
+                  int top_k, hipStream_t stream);
+void kt_moe_mlp(const void* x, long x_stride, const void* w_gate_up,
+                const void* w_down, const void* weights,
+                const void* expert_count, const void* expert_rows, void* h,
+                void* part, void* out, int T, int D, int I, int E, int top_k,
+                int S, hipStream_t stream);
+
 }  // extern "C"

@@ -1,0 +1,413 @@
+// Routed expert MLP for decode (gfx950 / CDNA4): top-k routing, the experts'
+// gate/up GEMM with a fused SwiGLU, the down GEMM and the top-k combine, for
+// 1 <= T <= 32 tokens of bf16 x. Four launches, no atomics, no host sync:
+//
+//   moe_route           router logits [T, E] -> sel [T, k], weights [T, k]
+//                       and the routing table expert_count [E],
+//                       expert_rows [E, 32]
+//   moe_gemm<true>      h[t, j, :]  = bf16(silu(x_t Wg_e^T) * (x_t Wu_e^T))
+//   moe_gemm<false>     part[s, t, j, :] = w[t, j] * (h[t, j, Ks] Wd_e[:, Ks]^T)
+//   moe_combine         out[t, :] = bf16(sum_s sum_j part[s, t, j, :])
+//
+// with e = sel[t, j]. A pair p = t * k + j names a (token, k-slot); h and the
+// partials are indexed by it, and expert_rows[e] lists the pairs routed to
+// expert e in token order.
+//
+// The two GEMMs are one kernel template. Per workgroup (4 waves) = (128
+// output columns, expert, K slice):
+//  - expert_count[e] == 0 returns before the first weight load: an expert
+//    nobody picked costs no HBM traffic and its weights cannot reach the
+//    output.
+//  - Each token picks an expert at most once, so an expert has at most T <= 32
+//    rows: one 32-row MFMA tile. The rows are gathered through the table into
+//    an LDS image shared by the four waves, in chunks of four steps (256 or
+//    512 k), double buffered, one barrier per chunk. Rows past the count are zeros and are
+//    never loaded (a raw buffer load past its resource returns zeros without
+//    a memory request).
+//  - A wave owns 32 output columns = 32 weight rows. Lane (r, h) streams row
+//    n0 + r: a 16 B load is 8 consecutive k, which is the lane's B fragment
+//    of one mfma_f32_32x32x16_bf16 (k = 16 s + 8 h + j), so weights need no
+//    permutation, go straight to VGPRs and never touch LDS. A step is 8 such
+//    loads per lane: 64 k of the gate row and of the up row (two
+//    accumulators), or 128 k of the down row. Three steps (24 loads per
+//    lane) are in flight ahead of the one in use.
+//  - The accumulator has the output column on the lane and the tile row in
+//    the registers, so SwiGLU and the routing weight are lane-local.
+//  - Only the down GEMM splits K (blockIdx.z): a split gate/up GEMM could not
+//    apply SwiGLU in its epilogue. The split factor comes from the shapes
+//    alone (kt_moe_down_plan), the partials are written with plain stores
+//    and summed in index order: bit-identical run to run, and a token's
+//    result does not depend on the batch it is computed in.
+//
+// Safety: every load of x, h and the weights goes through a buffer resource
+// of the operand's exact size. Table entries are device data: a count is
+// clamped to 32 and a pair outside [0, T k) is treated as an empty row, so
+// no store leaves h or the partials. Every index that scales with E * N * K
+// is 64-bit.
+//
+// No torch headers here; kt_launchers.h declares the extern "C" launchers.
+
+#include <hip/hip_runtime.h>
+
+#include "device_common.h"
+#include "kt_launchers.h"
+
+#define MOE_THREADS 256
+#define MOE_BN 128                  // output columns per workgroup
+#define MOE_ROWS 32                 // rows of an expert's tile (max T)
+#define MOE_MAX_E 64
+
+namespace {
+
+// ---------------------------------------------------------------------------
+// Routing
+// ---------------------------------------------------------------------------
+
+// exp(v - m) for v <= m in fp32. v == m is 1 (infinities included); the
+// rounding error of v - m is recovered (TwoSum) and applied to first order,
+// so the result is as accurate as expf itself for any spread of the logits.
+__device__ __forceinline__ float exp_diff(float v, float m) {
+  if (v == m) return 1.f;
+  const float d = v - m;
+  if (d == -INFINITY) return 0.f;
+  const float b = -m;
+  const float bb = d - v;
+  const float err = (v - (d - bb)) + (b - bb);
+  return expf(d) * (1.f + err);
+}
+
+// One workgroup. Pass 1, a wave per token and a lane per expert: rank the
+// logits (descending, equal logits lowest index first, NaN as -inf), write
+// the k best and their softmax. Pass 2, a wave per expert and a lane per
+// token: a ballot of the tokens that picked the expert gives its count and,
+// by prefix count, each pair's row in token order.
+__global__ __launch_bounds__(MOE_THREADS) void moe_route_kernel(
+    const void* __restrict__ logits, int is_bf16, int* __restrict__ sel,
+    float* __restrict__ weights, int* __restrict__ expert_count,
+    int* __restrict__ expert_rows, int T, int E, int top_k) {
+  __shared__ signed char slot_of[MOE_ROWS][MOE_MAX_E];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+  for (int t = wave; t < T; t += MOE_THREADS / 64) {  // wave-uniform
+    float v = -INFINITY;
+    if (lane < E) {
+      v = is_bf16 ? bf2f(((const u16*)logits)[t * E + lane])
+                  : ((const float*)logits)[t * E + lane];
+      if (v != v) v = -INFINITY;
+    }
+    int rank = 0;
+    for (int o = 0; o < E; ++o) {
+      const float vo = __shfl(v, o);
+      rank += (vo > v || (vo == v && o < lane)) ? 1 : 0;
+    }
+    const bool picked = lane < E && rank < top_k;
+    // the picked logits in slot order: every lane sums them the same way
+    float m = 0.f, sum = 0.f;
+    for (int j = 0; j < top_k; ++j) {
+      const unsigned long long b = __ballot(lane < E && rank == j);
+      const float vj = __shfl(v, __ffsll((long long)b) - 1);
+      if (j == 0) m = vj;
+      sum += exp_diff(vj, m);
+    }
+    if (picked) {
+      sel[t * top_k + rank] = lane;
+      weights[t * top_k + rank] = exp_diff(v, m) / sum;
+    }
+    if (lane < E) slot_of[t][lane] = picked ? (signed char)rank : (signed char)-1;
+  }
+  __syncthreads();
+
+  for (int e = wave; e < E; e += MOE_THREADS / 64) {
+    const int s = lane < T ? (int)slot_of[lane][e] : -1;
+    const unsigned long long mask = __ballot(s >= 0);
+    const int pos = __popcll(mask & ((1ull << lane) - 1ull));
+    if (s >= 0) expert_rows[e * MOE_ROWS + pos] = lane * top_k + s;
+    if (lane == 0) expert_count[e] = __popcll(mask);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The routed GEMMs
+// ---------------------------------------------------------------------------
+
+struct WStep {
+  vec4w v[8];
+};
+
+// Raw buffer loads: a lane whose offset is at or past the resource's size
+// gets zeros and makes no memory request, so empty rows, the tail of a K
+// slice and the prefetch past its end need no branch.
+#define MOE_RSRC_FLAGS 0x00020000  // gfx9 raw buffer, 32-bit data format
+#define MOE_OOB 0x80000000u        // every resource here is < 2 GiB
+
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+
+__device__ __forceinline__ vec4w buf_load(rsrc_t rs, unsigned off) {
+  return __builtin_bit_cast(
+      vec4w, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0));
+}
+
+__device__ __forceinline__ bf16x8 frag(vec4w v) {
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// GU: a = x [a_rows, K] (row stride a_stride), w = w_gate_up [E, 2N, K],
+//     writes h [npairs, N].
+// !GU: a = h [npairs, K], w = w_down [E, N, K], writes part [S, npairs, N]
+//     scaled by route_w [npairs].
+template <bool GU>
+__global__ __launch_bounds__(MOE_THREADS, 2) void moe_gemm_kernel(
+    const u16* __restrict__ a, long a_stride, int a_rows,
+    const u16* __restrict__ w, const int* __restrict__ expert_count,
+    const int* __restrict__ expert_rows, const float* __restrict__ route_w,
+    u16* __restrict__ hout, float* __restrict__ part, int top_k, int N, int K,
+    int npairs, int steps_per_split) {
+  constexpr int KS = GU ? 64 : 128;   // k per step
+  constexpr int NU = KS / 16;         // MFMA k-steps per step
+  // Steps per LDS chunk of the A rows: the ring's depth, so that the
+  // unrolled chunk rotates the ring once round and no register is copied.
+  constexpr int SPC = 4;
+  constexpr int CK = SPC * KS;        // k per chunk
+  constexpr int LDA = CK * 2 + 16;    // LDS row stride in bytes, 16 B pad
+  constexpr int PP = CK / 8;          // 16 B pieces per row
+  constexpr int RP = MOE_THREADS / PP;  // rows per staging pass
+  constexpr int NI = MOE_ROWS / RP;     // staging passes
+  __shared__ __attribute__((aligned(16))) unsigned char as[2 * MOE_ROWS * LDA];
+  __shared__ int pair_s[MOE_ROWS];
+
+  const int e = blockIdx.y;
+  int count = expert_count[e];
+  if (count <= 0) return;  // block-uniform, before the first weight load
+  count = count > MOE_ROWS ? MOE_ROWS : count;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31;  // MFMA row/column index of this lane
+  const int h = lane >> 5;  // lane half
+
+  if (tid < MOE_ROWS) {
+    int p = tid < count ? expert_rows[e * MOE_ROWS + tid] : -1;
+    if (p < 0 || p >= npairs) p = -1;
+    pair_s[tid] = p;
+  }
+  __syncthreads();
+
+  // this workgroup's K slice, in steps (block-uniform)
+  const int t0 = (int)blockIdx.z * steps_per_split;
+  int nt = K / KS - t0;
+  nt = nt > steps_per_split ? steps_per_split : nt;
+  nt = nt < 0 ? 0 : nt;
+  const int nchunks = (nt + SPC - 1) / SPC;
+  const long k0 = (long)(nt > 0 ? t0 : 0) * KS;  // inside the row
+  const int klen = nt * KS;
+
+  // The wave's 32 weight rows from column k0 on as one resource (N is a
+  // multiple of 128: every row exists). For gate/up a second resource holds
+  // the 32 up rows, N rows further on.
+  const long rows_e = GU ? 2L * N : (long)N;
+  const long n0 = (long)blockIdx.x * MOE_BN + wave * 32;  // wave-uniform
+  const u16* wb = w + ((size_t)e * rows_e + n0) * K + k0;
+  const int wbytes = (int)((31L * K + (K - k0)) * 2);
+  const rsrc_t wrs0 = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<u16*>(wb), 0, wbytes, MOE_RSRC_FLAGS);
+  const rsrc_t wrs1 = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<u16*>(GU ? wb + (size_t)N * K : wb), 0, wbytes,
+      MOE_RSRC_FLAGS);
+  const unsigned woff = (unsigned)(r * (long)K * 2) + 16 * h;
+  auto wstep = [&](int t) {  // step t of the slice, zeros past its end
+    const unsigned off = t < nt ? woff + (unsigned)t * (KS * 2) : MOE_OOB;
+    WStep o;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      o.v[u] = buf_load(wrs0, off + 32 * u);
+      if constexpr (GU) o.v[4 + u] = buf_load(wrs1, off + 32 * u);
+    }
+    return o;
+  };
+
+  // A staging: thread -> 16 B piece p of rows row0 + RP * i of a chunk,
+  // gathered through the table. The resource is the whole operand; empty
+  // rows and pieces past the slice come back as zeros.
+  const int p = tid % PP;
+  const int row0 = tid / PP;
+  const rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<u16*>(a), 0, (int)(((long)(a_rows - 1) * a_stride + K) * 2),
+      MOE_RSRC_FLAGS);
+  unsigned abase[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int pr = pair_s[row0 + RP * i];
+    const long src = GU ? pr / top_k : pr;  // x row of the token, or h row
+    abase[i] = pr >= 0 && src < a_rows
+                   ? (unsigned)((src * a_stride + k0 + p * 8) * 2)
+                   : MOE_OOB;
+  }
+  vec4w ar[NI];
+  auto afetch = [&](int c) {
+    const bool kok = c * CK + p * 8 < klen;  // the piece is in the slice
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+      ar[i] = buf_load(ars, kok && abase[i] != MOE_OOB
+                                ? abase[i] + (unsigned)c * (CK * 2)
+                                : MOE_OOB);
+  };
+  auto awrite = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+      *reinterpret_cast<vec4w*>(
+          &as[(buf * MOE_ROWS + row0 + RP * i) * LDA + p * 16]) = ar[i];
+  };
+
+  f32x16 acc0, acc1;  // gate and up, or acc0 alone
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
+
+  // weight ring: w0 is the step in use, w1..w3 are in flight
+  afetch(0);
+  WStep w0 = wstep(0), w1 = wstep(1), w2 = wstep(2), w3 = wstep(3);
+  awrite(0);
+  __syncthreads();
+
+  // Every chunk runs all of its steps: a step past the slice multiplies the
+  // zeros awrite left by the zeros wstep returned.
+  for (int c = 0; c < nchunks; ++c) {  // block-uniform trip count
+    afetch(c + 1);
+    const unsigned char* ab = &as[((c & 1) * MOE_ROWS + r) * LDA + 16 * h];
+#pragma unroll
+    for (int tl = 0; tl < SPC; ++tl) {
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        const bf16x8 av = *reinterpret_cast<const bf16x8*>(
+            ab + tl * (KS * 2) + 32 * u);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, frag(w0.v[u]),
+                                                       acc0, 0, 0, 0);
+        if constexpr (GU)
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              av, frag(w0.v[4 + u]), acc1, 0, 0, 0);
+      }
+      w0 = w1;
+      w1 = w2;
+      w2 = w3;
+      w3 = wstep(c * SPC + tl + 4);
+    }
+    awrite((c + 1) & 1);
+    __syncthreads();
+  }
+
+  // register i holds tile row (i & 3) + 8 * (i >> 2) + 4h of column n
+  const long n = n0 + r;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int pr = pair_s[(i & 3) + 8 * (i >> 2) + 4 * h];
+    if (pr < 0) continue;
+    if constexpr (GU) {
+      const float g = acc0[i];
+      const float s = g / (1.f + expf(-g));
+      const __bf16 b = (__bf16)(s * acc1[i]);
+      hout[(size_t)pr * N + n] = __builtin_bit_cast(u16, b);
+    } else {
+      part[((size_t)blockIdx.z * npairs + pr) * N + n] = acc0[i] * route_w[pr];
+    }
+  }
+}
+
+// out[t, d] = bf16(sum over s, then j, of part[s, t, j, d]), in that order.
+// Every (s, t, j) slab was written: each pair belongs to one expert's table.
+__global__ __launch_bounds__(256) void moe_combine_kernel(
+    const float* __restrict__ part, u16* __restrict__ out, int T, int D,
+    int top_k, int S) {
+  const int D4 = D / 4;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)T * D4) return;
+  const int t = (int)(i / D4);
+  const int d = (int)(i % D4) * 4;
+  float4 acc;
+  for (int s = 0; s < S; ++s) {
+    for (int j = 0; j < top_k; ++j) {
+      const float4 v = *reinterpret_cast<const float4*>(
+          part + (((size_t)s * T + t) * top_k + j) * D + d);
+      if (s == 0 && j == 0) {
+        acc = v;
+      } else {
+        acc.x += v.x;
+        acc.y += v.y;
+        acc.z += v.z;
+        acc.w += v.w;
+      }
+    }
+  }
+  const __bf16 b0 = (__bf16)acc.x, b1 = (__bf16)acc.y, b2 = (__bf16)acc.z,
+               b3 = (__bf16)acc.w;
+  vec2w o;
+  o[0] = (unsigned)__builtin_bit_cast(u16, b0) |
+         ((unsigned)__builtin_bit_cast(u16, b1) << 16);
+  o[1] = (unsigned)__builtin_bit_cast(u16, b2) |
+         ((unsigned)__builtin_bit_cast(u16, b3) << 16);
+  *reinterpret_cast<vec2w*>(out + (size_t)t * D + d) = o;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The down GEMM's split-K factor. With T = 1 only top_k experts are active,
+// so the smallest factor that still gives each of the chip's 256 CUs a
+// workgroup is ceil(256 / (D/128 * top_k)); slices of at least four 128-k
+// tiles, at most 8 slabs per pair to sum. A function of the shapes alone
+// (E does not enter: idle experts' workgroups exit at once).
+int kt_moe_down_plan(long D, long I, int E, int top_k) {
+  (void)E;
+  const long act = (D / MOE_BN) * top_k;
+  const long kt = I / 128;
+  long s = (256 + act - 1) / act;
+  if (s > kt / 4) s = kt / 4;
+  if (s > 8) s = 8;
+  if (s < 1) s = 1;
+  return (int)s;
+}
+
+// logits: [T, E] contiguous, bf16 (is_bf16 != 0) or fp32; sel, weights:
+// [T, top_k] int32 / fp32; expert_count: [E] int32; expert_rows: [E, 32]
+// int32. The binding has checked 1 <= T <= 32, 1 <= top_k <= E <= 64.
+void kt_moe_route(const void* logits, int is_bf16, void* sel, void* weights,
+                  void* expert_count, void* expert_rows, int T, int E,
+                  int top_k, hipStream_t stream) {
+  hipLaunchKernelGGL(moe_route_kernel, dim3(1), dim3(MOE_THREADS), 0, stream,
+                     logits, is_bf16, (int*)sel, (float*)weights,
+                     (int*)expert_count, (int*)expert_rows, T, E, top_k);
+}
+
+// x: [T, D] bf16, row stride x_stride elements; w_gate_up: [E, 2I, D] and
+// w_down: [E, D, I] bf16 contiguous; weights, expert_count, expert_rows: as
+// kt_moe_route wrote them; h: [T, top_k, I] bf16 and part: [S, T, top_k, D]
+// fp32 scratch; out: [T, D] bf16. The binding has checked 1 <= T <= 32,
+// D % 128 == I % 128 == 0, both <= 2^16, 1 <= S <= 64 and the alignments.
+void kt_moe_mlp(const void* x, long x_stride, const void* w_gate_up,
+                const void* w_down, const void* weights,
+                const void* expert_count, const void* expert_rows, void* h,
+                void* part, void* out, int T, int D, int I, int E, int top_k,
+                int S, hipStream_t stream) {
+  const int np = T * top_k;
+  hipLaunchKernelGGL(moe_gemm_kernel<true>,
+                     dim3((unsigned)(I / MOE_BN), (unsigned)E, 1),
+                     dim3(MOE_THREADS), 0, stream, (const u16*)x, x_stride, T,
+                     (const u16*)w_gate_up, (const int*)expert_count,
+                     (const int*)expert_rows, (const float*)nullptr, (u16*)h,
+                     (float*)nullptr, top_k, I, D, np, D / 64);
+  const int kt = I / 128;
+  hipLaunchKernelGGL(moe_gemm_kernel<false>,
+                     dim3((unsigned)(D / MOE_BN), (unsigned)E, (unsigned)S),
+                     dim3(MOE_THREADS), 0, stream, (const u16*)h, (long)I, np,
+                     (const u16*)w_down, (const int*)expert_count,
+                     (const int*)expert_rows, (const float*)weights,
+                     (u16*)nullptr, (float*)part, top_k, D, I, np,
+                     (kt + S - 1) / S);
+  const long n4 = (long)T * (D / 4);
+  hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n4 + 255) / 256)),
+                     dim3(256), 0, stream, (const float*)part, (u16*)out, T, D,
+                     top_k, S);
+}
+
+}  // extern "C"

@@ -35,7 +35,9 @@ every other flag combines with it.
 --moe ExK converts the built dense model to a mixture of E experts, top K
 (models.convert_to_moe: MoEMLP, eager decode); --moe-fused then fuses it
 (models.fuse_moe: the routed-GEMM decode kernels, captured decode graph up to
---batch 32).
+--batch 32). With --moe-fused, --weight-dtype fp8 quantises after fusing, so
+the stacked expert weights become e4m3 too (the W8A16 routed GEMMs); an
+unfused MoE's experts stay in the model's dtype.
 """
 import argparse
 import json
@@ -174,7 +176,8 @@ def main():
 
     dev = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     model, cfg = build_model(args.model, dev)
-    if args.weight_dtype == "fp8":
+    fp8_after_fuse = args.weight_dtype == "fp8" and args.moe_fused
+    if args.weight_dtype == "fp8" and not fp8_after_fuse:
         from kubetorch_amd.models import quantize_weights_fp8
 
         model = quantize_weights_fp8(model, inplace=True)
@@ -186,6 +189,10 @@ def main():
         model = model.to(p.device, p.dtype).eval()
         if args.moe_fused:
             model = fuse_moe(model, inplace=True)
+    if fp8_after_fuse:  # the fused experts' weights are quantised too
+        from kubetorch_amd.models import quantize_weights_fp8
+
+        model = quantize_weights_fp8(model, inplace=True)
     run = (model, cfg, args.batch, args.prompt, args.new)
     mode = dict(kv=args.kv, page_size=args.page_size,
                 num_splits=args.num_splits)

@@ -159,7 +159,12 @@ class FusedMoEMLP(nn.Module):
     weights stay fp32, the top-k sum is carried in fp32 and rounded once, and
     h = silu(gate) * up is rounded once from fp32 (MoEMLP rounds the routing
     weights, gate/up, each expert's output and every partial sum to the
-    model's dtype). Equal router logits go to the lowest expert index."""
+    model's dtype). Equal router logits go to the lowest expert index.
+
+    quantize_fp8_() turns the two weights into e4m3 buffers of the same names
+    with fp32 buffers w_gate_up_scale [E, 2I] and w_down_scale [E, D]
+    (ops.quantize_weight_fp8 per expert); a dtype cast of the model then
+    leaves them as they are, device moves apply."""
 
     # Calls of more rows than this run ops.moe_mlp's composition, which syncs
     # the host: the serving engine captures no decode graph above it.
@@ -198,13 +203,69 @@ class FusedMoEMLP(nn.Module):
             [ex.w_down.weight.detach() for ex in moe.experts]))
         return new
 
+    @property
+    def is_fp8(self):
+        return self.w_gate_up.dtype == ops.W8_DTYPE
+
+    @torch.no_grad()
+    def quantize_fp8_(self):
+        """Quantise the experts' weights in place, expert by expert (the fp32
+        temporary is one expert's matrix); each bf16 tensor is dropped as
+        soon as its replacement exists. The scale values are validated here,
+        once, on the host."""
+        if self.is_fp8:
+            return self
+        for name in ("w_gate_up", "w_down"):
+            w = getattr(self, name)
+            q = torch.empty(w.shape, dtype=ops.W8_DTYPE, device=w.device)
+            scale = torch.empty(w.shape[:2], dtype=torch.float32,
+                                device=w.device)
+            for e in range(w.shape[0]):
+                q[e], scale[e] = ops.quantize_weight_fp8(w[e])
+            self.set_fp8_(name, q, scale)
+        return self
+
+    def set_fp8_(self, name, q, scale):
+        """Install e4m3 bytes q [E, N, K] and their row scales [E, N] as the
+        buffers `name` and `name`_scale, replacing the parameter."""
+        if q.dtype != ops.W8_DTYPE or scale.dtype != torch.float32 \
+                or tuple(scale.shape) != tuple(q.shape[:2]):
+            raise ValueError(f"{name}: expected e4m3 [E, N, K] and fp32 "
+                             "[E, N] scales")
+        ops._check_w8_scale_values(scale)
+        self._parameters.pop(name, None)
+        self._buffers.pop(name, None)
+        self._buffers.pop(name + "_scale", None)
+        self.register_buffer(name, q.contiguous())
+        self.register_buffer(name + "_scale", scale.contiguous())
+
+    def _apply(self, fn, recurse=True):
+        # device moves apply; dtype casts must not touch the fp8 bytes or
+        # round the scales
+        if not self.is_fp8:
+            return super()._apply(fn, recurse)
+        names = ("w_gate_up", "w_down", "w_gate_up_scale", "w_down_scale")
+        old = {n: getattr(self, n) for n in names}
+        super()._apply(fn, recurse)
+        for n, t in old.items():
+            new = getattr(self, n)
+            if new.dtype != t.dtype:
+                setattr(self, n, t.to(new.device))
+        return self
+
     def forward(self, x):
+        if self.is_fp8:
+            return ops.moe_mlp(x, self.router(x), self.w_gate_up, self.w_down,
+                               self.top_k,
+                               w_gate_up_scale=self.w_gate_up_scale,
+                               w_down_scale=self.w_down_scale)
         return ops.moe_mlp(x, self.router(x), self.w_gate_up, self.w_down,
                            self.top_k)
 
     def extra_repr(self):
         return (f"dim={self.dim}, intermediate={self.intermediate}, "
-                f"n_experts={self.n_experts}, top_k={self.top_k}")
+                f"n_experts={self.n_experts}, top_k={self.top_k}"
+                + (", weight=e4m3" if self.is_fp8 else ""))
 
 
 def fuse_moe(model, inplace=False):

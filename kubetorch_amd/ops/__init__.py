@@ -1759,17 +1759,22 @@ def moe_route(router_logits, top_k):
     return sel.view(*lead, top_k), w.view(*lead, top_k)
 
 
-def _moe_kernel_ok(x, router_logits, w_gate_up, w_down, top_k):
+def _moe_kernel_ok(x, router_logits, w_gate_up, w_down, top_k,
+                   w_gate_up_scale=None, w_down_scale=None):
     """What the kernels take; everything else runs the composition."""
     E, D, I = w_down.shape
+    wdt = W8_DTYPE if w_gate_up_scale is not None else torch.bfloat16
     if not (x.is_cuda and x.dtype == torch.bfloat16
-            and w_gate_up.dtype == torch.bfloat16
-            and w_down.dtype == torch.bfloat16
+            and w_gate_up.dtype == wdt and w_down.dtype == wdt
             and router_logits.dtype in (torch.bfloat16, torch.float32)
             and E <= MOE_MAX_EXPERTS and top_k <= MOE_MAX_TOP_K
             and D % MOE_DIM_MULTIPLE == 0 and I % MOE_DIM_MULTIPLE == 0
             and 0 < D <= MOE_MAX_DIM and 0 < I <= MOE_MAX_DIM
             and w_gate_up.is_contiguous() and w_down.is_contiguous()):
+        return False
+    if w_gate_up_scale is not None and not (
+            w_down_scale is not None and w_gate_up_scale.is_contiguous()
+            and w_down_scale.is_contiguous()):
         return False
     x2 = _w8_rows(x, D)
     if x2 is None:
@@ -1781,20 +1786,29 @@ def _moe_kernel_ok(x, router_logits, w_gate_up, w_down, top_k):
                             and x2.stride(0) % 8 == 0)))
 
 
-def _moe_mlp_ref(x2, logits2, w_gate_up, w_down, top_k):
+def _moe_mlp_ref(x2, logits2, w_gate_up, w_down, top_k, w_gate_up_scale=None,
+                 w_down_scale=None):
     """The composition: route, then per picked expert gather its tokens, run
     gate/up, SwiGLU and down, and add the weighted rows. bf16 and fp16 inputs
-    compute in fp32 with h rounded once to x's dtype, as the kernel does. The
+    compute in fp32 with h rounded once to x's dtype, as the kernel does. fp8
+    weights are dequantised one picked expert at a time (exact in fp32). The
     nonzero() syncs the host."""
     I = w_down.shape[2]
     ct = torch.float64 if x2.dtype == torch.float64 else torch.float32
+
+    def mat(w, scale, e):
+        if scale is None:
+            return w[e].to(ct)
+        return w[e].to(ct).mul_(scale[e].to(ct)[:, None])
+
     sel, weights = _moe_route_ref(logits2, top_k)
     out = torch.zeros(x2.shape, dtype=ct, device=x2.device)
     for e in sel.unique().tolist():
         tok, kth = (sel == e).nonzero(as_tuple=True)
-        gu = torch.nn.functional.linear(x2[tok].to(ct), w_gate_up[e].to(ct))
+        gu = torch.nn.functional.linear(x2[tok].to(ct),
+                                        mat(w_gate_up, w_gate_up_scale, e))
         h = (torch.nn.functional.silu(gu[:, :I]) * gu[:, I:]).to(x2.dtype)
-        y = torch.nn.functional.linear(h.to(ct), w_down[e].to(ct))
+        y = torch.nn.functional.linear(h.to(ct), mat(w_down, w_down_scale, e))
         out.index_add_(0, tok, y * weights[tok, kth].to(ct).unsqueeze(-1))
     return out.to(x2.dtype)
 
@@ -1805,7 +1819,8 @@ def moe_down_splits(dim, intermediate, n_experts, top_k):
     return int(_ext().moe_down_splits(dim, intermediate, n_experts, top_k))
 
 
-def moe_mlp(x, router_logits, w_gate_up, w_down, top_k, num_splits=None):
+def moe_mlp(x, router_logits, w_gate_up, w_down, top_k, num_splits=None,
+            w_gate_up_scale=None, w_down_scale=None):
     """Top-k mixture of SwiGLU experts for inference:
 
         out[t] = round(sum_j weights[t, j] * (h[t, j] @ w_down[e].T)),
@@ -1819,25 +1834,62 @@ def moe_mlp(x, router_logits, w_gate_up, w_down, top_k, num_splits=None):
     w_down [E, D, I] in x's dtype. Inference-only: x must not require grad
     while grad is enabled.
 
+    FP8 expert weights: both weights torch.float8_e4m3fn with
+    w_gate_up_scale [E, 2I] and w_down_scale [E, D], fp32 powers of two in
+    [2^-40, 2^40] (quantize_weight_fp8 per expert). The matrices above are
+    then float(q) * scale[..., None], which are exactly bf16; x is bf16,
+    fp16, fp32 or fp64. Both weights are e4m3 with both scales, or neither
+    is: any other mix raises ValueError, as do scales of the wrong dtype,
+    shape or device. Scale values are checked on the CPU only (the model
+    quantiser checks them once).
+
     bf16 GPU x with 1 <= T <= 32 rows, E <= 64, top_k <= 8, D and I multiples
-    of 128, contiguous weights, bf16 or fp32 logits and 16-byte aligned rows
-    runs the gfx950 kernels: four launches, no host sync (capturable in a
-    graph), only the picked experts' weights are read, bit-identical run to
-    run, a token's result independent of the other tokens in the call. Any
-    other valid input, the CPU included, runs a torch composition that loops
-    over the picked experts and syncs the host. num_splits overrides the
-    down GEMM's split-K factor (tests); the composition ignores it."""
+    of 128, contiguous weights (and scales), bf16 or fp32 logits and 16-byte
+    aligned rows runs the gfx950 kernels: four launches, no host sync
+    (capturable in a graph), only the picked experts' weights are read, bit-
+    identical run to run, a token's result independent of the other tokens in
+    the call. Any other valid input, the CPU included, runs a torch
+    composition that loops over the picked experts and syncs the host.
+    num_splits overrides the down GEMM's split-K factor (tests); the
+    composition ignores it."""
+    fp8 = any(torch.is_tensor(w) and w.dtype in _FLOAT8_DTYPES
+              for w in (w_gate_up, w_down)) \
+        or w_gate_up_scale is not None or w_down_scale is not None
     for name, w in (("w_gate_up", w_gate_up), ("w_down", w_down)):
         if not torch.is_tensor(w) or w.dim() != 3 \
-                or not w.is_floating_point() or w.dtype in _FLOAT8_DTYPES:
-            raise ValueError(f"{name} must be a 3-D floating-point tensor")
+                or not w.is_floating_point() \
+                or (w.dtype in _FLOAT8_DTYPES and w.dtype != W8_DTYPE):
+            raise ValueError(f"{name} must be a 3-D floating-point tensor "
+                             "(of the float8 types, float8_e4m3fn only)")
+    if fp8 and not (w_gate_up.dtype == w_down.dtype == W8_DTYPE
+                    and w_gate_up_scale is not None
+                    and w_down_scale is not None):
+        raise ValueError("fp8 expert weights need both w_gate_up and w_down "
+                         "as float8_e4m3fn and both scales; other weights "
+                         "take no scales")
     E, D, I = w_down.shape
     if tuple(w_gate_up.shape) != (E, 2 * I, D):
         raise ValueError(f"w_gate_up must be [{E}, {2 * I}, {D}] for w_down "
                          f"{tuple(w_down.shape)}, got {tuple(w_gate_up.shape)}")
     if not torch.is_tensor(x) or x.dim() < 1 or x.shape[-1] != D:
         raise ValueError(f"x must be a tensor [..., {D}]")
-    if not (x.dtype == w_gate_up.dtype == w_down.dtype):
+    if fp8:
+        if x.dtype not in (torch.bfloat16, torch.float16, torch.float32,
+                           torch.float64):
+            raise ValueError("x must be bf16, fp16, fp32 or fp64 with fp8 "
+                             f"weights, got {x.dtype}")
+        for name, sc, w in (("w_gate_up_scale", w_gate_up_scale, w_gate_up),
+                            ("w_down_scale", w_down_scale, w_down)):
+            if not torch.is_tensor(sc) or sc.dtype != torch.float32:
+                raise ValueError(f"{name} must be an fp32 tensor")
+            if tuple(sc.shape) != tuple(w.shape[:2]):
+                raise ValueError(f"{name} must be {tuple(w.shape[:2])}, got "
+                                 f"{tuple(sc.shape)}")
+            if sc.device != w.device:
+                raise ValueError(f"{name} must be on its weight's device")
+            if not sc.is_cuda and sc.device.type != "meta":
+                _check_w8_scale_values(sc)
+    elif not (x.dtype == w_gate_up.dtype == w_down.dtype):
         raise ValueError("x, w_gate_up and w_down must have one dtype, got "
                          f"{x.dtype}, {w_gate_up.dtype}, {w_down.dtype}")
     _check_moe_route(router_logits, top_k)
@@ -1855,13 +1907,16 @@ def moe_mlp(x, router_logits, w_gate_up, w_down, top_k, num_splits=None):
     w_gate_up, w_down = w_gate_up.detach(), w_down.detach()
     if x.numel() == 0:
         return torch.empty_like(x)
-    if _moe_kernel_ok(x, router_logits, w_gate_up, w_down, top_k):
+    if _moe_kernel_ok(x, router_logits, w_gate_up, w_down, top_k,
+                      w_gate_up_scale, w_down_scale):
         out = _ext().moe_mlp(_w8_rows(x, D),
                              router_logits.reshape(-1, E).contiguous(),
-                             w_gate_up, w_down, top_k, int(num_splits or 0))
+                             w_gate_up, w_down, top_k, int(num_splits or 0),
+                             w_gate_up_scale, w_down_scale)
     else:
         out = _moe_mlp_ref(x.reshape(-1, D), router_logits.reshape(-1, E),
-                           w_gate_up, w_down, top_k)
+                           w_gate_up, w_down, top_k, w_gate_up_scale,
+                           w_down_scale)
     return out.view(x.shape)
 
 

@@ -909,19 +909,29 @@ std::vector<at::Tensor> moe_route(const at::Tensor& logits, int64_t top_k) {
 
 at::Tensor moe_mlp(const at::Tensor& x, const at::Tensor& logits,
                    const at::Tensor& w_gate_up, const at::Tensor& w_down,
-                   int64_t top_k, int64_t num_splits) {
+                   int64_t top_k, int64_t num_splits,
+                   const c10::optional<at::Tensor>& w_gate_up_scale,
+                   const c10::optional<at::Tensor>& w_down_scale) {
   // x: [T, D] bf16, last dim contiguous, row base and stride 16 B aligned;
-  // w_gate_up: [E, 2I, D] and w_down: [E, D, I] bf16 contiguous, D and I
-  // multiples of 128 up to 2^16 (ops.moe_mlp sends everything else to the
-  // composition). num_splits 0 is the kernel's own choice from the shapes.
+  // w_gate_up: [E, 2I, D] and w_down: [E, D, I] contiguous, both bf16 with
+  // no scales or both e4m3 with the fp32 row scales [E, 2I] and [E, D]; D
+  // and I multiples of 128 up to 2^16 (ops.moe_mlp sends everything else to
+  // the composition). num_splits 0 is the kernel's own choice from the
+  // shapes. The scale values are not looked at here (a device sync).
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
               "x must be [T, D] bf16 on GPU");
   const int64_t T = x.size(0), D = x.size(1);
+  const bool fp8 = w_gate_up.scalar_type() == at::kFloat8_e4m3fn;
   for (const at::Tensor* w : {&w_gate_up, &w_down})
     TORCH_CHECK(w->is_cuda() && w->device() == x.device() &&
-                    w->scalar_type() == at::kBFloat16 && w->dim() == 3 &&
-                    w->is_contiguous(),
-                "expert weights must be 3-D bf16, contiguous, on x's device");
+                    w->scalar_type() ==
+                        (fp8 ? at::kFloat8_e4m3fn : at::kBFloat16) &&
+                    w->dim() == 3 && w->is_contiguous(),
+                "expert weights must be 3-D, both bf16 or both "
+                "float8_e4m3fn, contiguous, on x's device");
+  TORCH_CHECK(w_gate_up_scale.has_value() == fp8 &&
+                  w_down_scale.has_value() == fp8,
+              "the two weight scales go with float8_e4m3fn weights only");
   const int64_t E = w_gate_up.size(0), I = w_down.size(2);
   TORCH_CHECK(w_gate_up.size(1) == 2 * I && w_gate_up.size(2) == D &&
                   w_down.size(0) == E && w_down.size(1) == D,
@@ -932,6 +942,18 @@ at::Tensor moe_mlp(const at::Tensor& x, const at::Tensor& logits,
   TORCH_CHECK(D >= 128 && D % 128 == 0 && D <= (1 << 16) && I >= 128 &&
                   I % 128 == 0 && I <= (1 << 16),
               "D and I must be multiples of 128 up to 2^16, got ", D, ", ", I);
+  if (fp8) {
+    const at::Tensor &sg = *w_gate_up_scale, &sd = *w_down_scale;
+    TORCH_CHECK(sg.scalar_type() == at::kFloat && sg.dim() == 2 &&
+                    sg.size(0) == E && sg.size(1) == 2 * I &&
+                    sg.is_contiguous() && sg.device() == x.device(),
+                "w_gate_up_scale must be [E, 2I] fp32, contiguous, on x's "
+                "device");
+    TORCH_CHECK(sd.scalar_type() == at::kFloat && sd.dim() == 2 &&
+                    sd.size(0) == E && sd.size(1) == D &&
+                    sd.is_contiguous() && sd.device() == x.device(),
+                "w_down_scale must be [E, D] fp32, contiguous, on x's device");
+  }
   const int64_t xs = T > 1 ? x.stride(0) : D;
   TORCH_CHECK(x.stride(1) == 1, "x's last dim must be contiguous");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
@@ -949,7 +971,9 @@ at::Tensor moe_mlp(const at::Tensor& x, const at::Tensor& logits,
   kt_moe_mlp(x.data_ptr(), (long)xs, w_gate_up.data_ptr(), w_down.data_ptr(),
              route[1].data_ptr(), route[2].data_ptr(), route[3].data_ptr(),
              h.data_ptr(), part.data_ptr(), out.data_ptr(), (int)T, (int)D,
-             (int)I, (int)E, (int)top_k, S, cur_stream(x));
+             (int)I, (int)E, (int)top_k, S, fp8 ? 1 : 0,
+             scale_ptr(w_gate_up_scale), scale_ptr(w_down_scale),
+             cur_stream(x));
   return out;
 }
 
@@ -1016,7 +1040,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("moe_route", &moe_route,
           "Top-k routing of [T, E] logits -> (sel, weights, count, rows)");
   mod.def("moe_mlp", &moe_mlp,
-          "Routed expert SwiGLU MLP of T <= 32 rows of bf16 x -> [T, D]");
+          "Routed expert SwiGLU MLP of T <= 32 rows of bf16 x -> [T, D]",
+          pybind11::arg("x"), pybind11::arg("router_logits"),
+          pybind11::arg("w_gate_up"), pybind11::arg("w_down"),
+          pybind11::arg("top_k"), pybind11::arg("num_splits"),
+          pybind11::arg("w_gate_up_scale") = pybind11::none(),
+          pybind11::arg("w_down_scale") = pybind11::none());
   mod.def("moe_down_splits", &moe_down_splits,
           "The split-K factor moe_mlp's down GEMM chooses for the shapes");
 }

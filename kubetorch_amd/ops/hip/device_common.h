@@ -57,3 +57,10 @@ __device__ __forceinline__ vec2w e4m3x4_to_bf16(unsigned int w) {
   o[1] = bf16_pair(__builtin_amdgcn_cvt_pk_f32_fp8(w, true));
   return o;
 }
+
+// 8 e4m3 bytes (two dwords) -> one bf16x8 MFMA fragment
+__device__ __forceinline__ bf16x8 frag_fp8(unsigned lo, unsigned hi) {
+  const vec2w a = e4m3x4_to_bf16(lo), b = e4m3x4_to_bf16(hi);
+  const vec4w o = {a[0], a[1], b[0], b[1]};
+  return __builtin_bit_cast(bf16x8, o);
+}

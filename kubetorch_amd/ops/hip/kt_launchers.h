@@ -115,6 +115,9 @@ void kt_linear_w8(const void* x, long x_stride, const void* wq,
                   int S, hipStream_t stream);
 
 // moe.hip. kt_moe_route writes the routing table that kt_moe_mlp reads.
+// fp8 != 0: the expert weights are e4m3 and the two scale arguments are
+// [E, 2I] and [E, D] fp32 device arrays; otherwise bf16 weights, and the
+// scales are not read.
 int kt_moe_down_plan(long D, long I, int E, int top_k);
 void kt_moe_route(const void* logits, int is_bf16, void* sel, void* weights,
                   void* expert_count, void* expert_rows, int T, int E,
@@ -123,6 +126,7 @@ void kt_moe_mlp(const void* x, long x_stride, const void* w_gate_up,
                 const void* w_down, const void* weights,
                 const void* expert_count, const void* expert_rows, void* h,
                 void* part, void* out, int T, int D, int I, int E, int top_k,
-                int S, hipStream_t stream);
+                int S, int fp8, const void* gate_up_scale,
+                const void* down_scale, hipStream_t stream);
 
 }  // extern "C"

@@ -49,13 +49,6 @@
 
 namespace {
 
-// 8 e4m3 bytes (two dwords) -> one bf16x8 MFMA fragment
-__device__ __forceinline__ bf16x8 frag_fp8(unsigned lo, unsigned hi) {
-  const vec2w a = e4m3x4_to_bf16(lo), b = e4m3x4_to_bf16(hi);
-  const vec4w o = {a[0], a[1], b[0], b[1]};
-  return __builtin_bit_cast(bf16x8, o);
-}
-
 struct WTile {
   vec4w v[4];
 };

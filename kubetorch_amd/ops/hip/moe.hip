@@ -39,6 +39,28 @@
 //    and summed in index order: bit-identical run to run, and a token's
 //    result does not depend on the batch it is computed in.
 //
+// FP8 expert weights (W8A16): the same template with a byte weight type.
+// w_gate_up and w_down are OCP e4m3 with one power-of-two fp32 scale per
+// expert and weight row; the work split, the early exit, the LDS image and
+// the epilogue's layout are those above. What changes is the data path:
+//  - A 16 B load is 16 consecutive k of the lane's row: its low 8 bytes are
+//    the B fragment of one k-step and its high 8 bytes that of the next
+//    (v_cvt_pk_f32_fp8 and the high half of each fp32: exact), so inside a
+//    128-k tile k-step 2u + e holds, on lane half h, element j:
+//        k = 32 u + 16 h + 8 e + j,
+//    and the A fragments are read from the LDS image with that permutation.
+//    The four loads of a tile are one 128 B line of the row.
+//  - A step is still 8 loads per lane, now 128 k of the gate and up rows or
+//    256 k of the down row, and the LDS chunks are 256 k for both (one
+//    barrier per 256 k, 33,920 B). The unpacked fragments cost registers the
+//    bf16 kernel does not need: gate/up keeps two steps (16 loads per lane)
+//    ahead of the one in use, down three (24, as bf16).
+//  - The down GEMM's K slices are counted in 128-k tiles for both weight
+//    types, so kt_moe_down_plan means the same; a 256-k step whose second
+//    tile lies past the slice loads zeros for it.
+//  - The scale multiplies the fp32 accumulator once in the epilogue (exact):
+//    gate and up before SwiGLU, down before the routing weight.
+//
 // Safety: every load of x, h and the weights goes through a buffer resource
 // of the operand's exact size. Table entries are device data: a count is
 // clamped to 32 and a pair outside [0, T k) is treated as an empty row, so
@@ -156,18 +178,30 @@ __device__ __forceinline__ bf16x8 frag(vec4w v) {
 //     writes h [npairs, N].
 // !GU: a = h [npairs, K], w = w_down [E, N, K], writes part [S, npairs, N]
 //     scaled by route_w [npairs].
-template <bool GU>
+// WT is the weight element: u16 (bf16) or unsigned char (e4m3, with one fp32
+// scale per weight row in w_scale [E, 2N] or [E, N], applied in the
+// epilogue). The K split is counted in units: a step, or for the e4m3 down
+// GEMM a 128-k tile (half a step), so both weight types split alike.
+template <bool GU, typename WT>
 __global__ __launch_bounds__(MOE_THREADS, 2) void moe_gemm_kernel(
     const u16* __restrict__ a, long a_stride, int a_rows,
-    const u16* __restrict__ w, const int* __restrict__ expert_count,
+    const WT* __restrict__ w, const float* __restrict__ w_scale,
+    const int* __restrict__ expert_count,
     const int* __restrict__ expert_rows, const float* __restrict__ route_w,
     u16* __restrict__ hout, float* __restrict__ part, int top_k, int N, int K,
-    int npairs, int steps_per_split) {
-  constexpr int KS = GU ? 64 : 128;   // k per step
-  constexpr int NU = KS / 16;         // MFMA k-steps per step
-  // Steps per LDS chunk of the A rows: the ring's depth, so that the
-  // unrolled chunk rotates the ring once round and no register is copied.
-  constexpr int SPC = 4;
+    int npairs, int units_per_split) {
+  constexpr bool W8 = sizeof(WT) == 1;
+  constexpr int ES = (int)sizeof(WT);
+  constexpr int NU = GU ? 4 : 8;      // 16 B loads per weight row and step
+  constexpr int KS = NU * 32 / ES;    // k per step: 64 / 128, e4m3 128 / 256
+  constexpr int UK = GU ? KS : 128;   // k per unit of the K split
+  // Steps in the register ring (one in use, the others in flight), steps per
+  // LDS chunk of the A rows and chunks per loop iteration: the unrolled
+  // iteration is whole turns of the ring, so no register is copied.
+  constexpr int R = W8 && GU ? 3 : 4;
+  constexpr int SPC = W8 ? (GU ? 2 : 1) : 4;
+  constexpr int CPI = W8 ? (GU ? 3 : 4) : 1;
+  static_assert(CPI * SPC % R == 0, "an iteration is whole turns of the ring");
   constexpr int CK = SPC * KS;        // k per chunk
   constexpr int LDA = CK * 2 + 16;    // LDS row stride in bytes, 16 B pad
   constexpr int PP = CK / 8;          // 16 B pieces per row
@@ -194,35 +228,50 @@ __global__ __launch_bounds__(MOE_THREADS, 2) void moe_gemm_kernel(
   }
   __syncthreads();
 
-  // this workgroup's K slice, in steps (block-uniform)
-  const int t0 = (int)blockIdx.z * steps_per_split;
-  int nt = K / KS - t0;
-  nt = nt > steps_per_split ? steps_per_split : nt;
+  // this workgroup's K slice, in units and in steps (block-uniform)
+  const int t0 = (int)blockIdx.z * units_per_split;
+  int nt = K / UK - t0;
+  nt = nt > units_per_split ? units_per_split : nt;
   nt = nt < 0 ? 0 : nt;
+  const long k0 = (long)(nt > 0 ? t0 : 0) * UK;  // inside the row
+  const int klen = nt * UK;
+  if constexpr (UK != KS) nt = (klen + KS - 1) / KS;  // units -> steps
   const int nchunks = (nt + SPC - 1) / SPC;
-  const long k0 = (long)(nt > 0 ? t0 : 0) * KS;  // inside the row
-  const int klen = nt * KS;
 
   // The wave's 32 weight rows from column k0 on as one resource (N is a
   // multiple of 128: every row exists). For gate/up a second resource holds
   // the 32 up rows, N rows further on.
   const long rows_e = GU ? 2L * N : (long)N;
   const long n0 = (long)blockIdx.x * MOE_BN + wave * 32;  // wave-uniform
-  const u16* wb = w + ((size_t)e * rows_e + n0) * K + k0;
-  const int wbytes = (int)((31L * K + (K - k0)) * 2);
+  const WT* wb = w + ((size_t)e * rows_e + n0) * K + k0;
+  const int wbytes = (int)((31L * K + (K - k0)) * ES);
   const rsrc_t wrs0 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<u16*>(wb), 0, wbytes, MOE_RSRC_FLAGS);
+      const_cast<WT*>(wb), 0, wbytes, MOE_RSRC_FLAGS);
   const rsrc_t wrs1 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<u16*>(GU ? wb + (size_t)N * K : wb), 0, wbytes,
+      const_cast<WT*>(GU ? wb + (size_t)N * K : wb), 0, wbytes,
       MOE_RSRC_FLAGS);
-  const unsigned woff = (unsigned)(r * (long)K * 2) + 16 * h;
+  const unsigned woff = (unsigned)(r * (long)K * ES) + 16 * h;
   auto wstep = [&](int t) {  // step t of the slice, zeros past its end
-    const unsigned off = t < nt ? woff + (unsigned)t * (KS * 2) : MOE_OOB;
     WStep o;
+    if constexpr (W8 && !GU) {
+      // two 128 B lines of the row; the slice may end after the first
+      const unsigned off0 =
+          t * KS < klen ? woff + (unsigned)t * KS : MOE_OOB;
+      const unsigned off1 =
+          t * KS + 128 < klen ? woff + (unsigned)t * KS + 128 : MOE_OOB;
 #pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      o.v[u] = buf_load(wrs0, off + 32 * u);
-      if constexpr (GU) o.v[4 + u] = buf_load(wrs1, off + 32 * u);
+      for (int u = 0; u < 4; ++u) {
+        o.v[u] = buf_load(wrs0, off0 + 32 * u);
+        o.v[4 + u] = buf_load(wrs0, off1 + 32 * u);
+      }
+    } else {
+      const unsigned off =
+          t < nt ? woff + (unsigned)t * (KS * ES) : MOE_OOB;
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        o.v[u] = buf_load(wrs0, off + 32 * u);
+        if constexpr (GU) o.v[4 + u] = buf_load(wrs1, off + 32 * u);
+      }
     }
     return o;
   };
@@ -260,55 +309,94 @@ __global__ __launch_bounds__(MOE_THREADS, 2) void moe_gemm_kernel(
           &as[(buf * MOE_ROWS + row0 + RP * i) * LDA + p * 16]) = ar[i];
   };
 
+  // the row scales of this lane's output column (e4m3 weights only)
+  float sc0 = 1.f, sc1 = 1.f;
+  if constexpr (W8) {
+    const float* sc = w_scale + (size_t)e * rows_e + n0 + r;
+    sc0 = sc[0];
+    if constexpr (GU) sc1 = sc[N];
+  }
+
   f32x16 acc0, acc1;  // gate and up, or acc0 alone
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
 
-  // weight ring: w0 is the step in use, w1..w3 are in flight
+  // weight ring: wr[0] is the step in use, the others are in flight
   afetch(0);
-  WStep w0 = wstep(0), w1 = wstep(1), w2 = wstep(2), w3 = wstep(3);
+  WStep wr[R];
+#pragma unroll
+  for (int i = 0; i < R; ++i) wr[i] = wstep(i);
   awrite(0);
   __syncthreads();
 
-  // Every chunk runs all of its steps: a step past the slice multiplies the
-  // zeros awrite left by the zeros wstep returned.
-  for (int c = 0; c < nchunks; ++c) {  // block-uniform trip count
-    afetch(c + 1);
-    const unsigned char* ab = &as[((c & 1) * MOE_ROWS + r) * LDA + 16 * h];
+  // Every chunk runs all of its steps, and every iteration all of its
+  // chunks: a step past the slice multiplies the zeros awrite left by the
+  // zeros wstep returned.
+  for (int c = 0; c < nchunks; c += CPI) {  // block-uniform trip count
 #pragma unroll
-    for (int tl = 0; tl < SPC; ++tl) {
+    for (int ci = 0; ci < CPI; ++ci) {
+      const int cc = c + ci;
+      afetch(cc + 1);
+      // bf16: k-step u of a step is k = 16 u + 8 h + j. e4m3: a 16 B load is
+      // two k-steps, so k-step 2u + e is k = 32 u + 16 h + 8 e + j, and the
+      // A fragments are read with the same permutation.
+      const unsigned char* ab =
+          &as[((cc & 1) * MOE_ROWS + r) * LDA + (W8 ? 32 : 16) * h];
 #pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        const bf16x8 av = *reinterpret_cast<const bf16x8*>(
-            ab + tl * (KS * 2) + 32 * u);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, frag(w0.v[u]),
-                                                       acc0, 0, 0, 0);
-        if constexpr (GU)
-          acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              av, frag(w0.v[4 + u]), acc1, 0, 0, 0);
+      for (int tl = 0; tl < SPC; ++tl) {
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+          if constexpr (W8) {
+            const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(
+                ab + tl * (KS * 2) + 64 * u);
+            const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(
+                ab + tl * (KS * 2) + 64 * u + 16);
+            const vec4w g = wr[0].v[u];
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                a0, frag_fp8(g[0], g[1]), acc0, 0, 0, 0);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                a1, frag_fp8(g[2], g[3]), acc0, 0, 0, 0);
+            if constexpr (GU) {
+              const vec4w v = wr[0].v[4 + u];
+              acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                  a0, frag_fp8(v[0], v[1]), acc1, 0, 0, 0);
+              acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                  a1, frag_fp8(v[2], v[3]), acc1, 0, 0, 0);
+            }
+          } else {
+            const bf16x8 av = *reinterpret_cast<const bf16x8*>(
+                ab + tl * (KS * 2) + 32 * u);
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, frag(wr[0].v[u]),
+                                                           acc0, 0, 0, 0);
+            if constexpr (GU)
+              acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                  av, frag(wr[0].v[4 + u]), acc1, 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int i = 0; i + 1 < R; ++i) wr[i] = wr[i + 1];
+        wr[R - 1] = wstep(cc * SPC + tl + R);
       }
-      w0 = w1;
-      w1 = w2;
-      w2 = w3;
-      w3 = wstep(c * SPC + tl + 4);
+      awrite((cc + 1) & 1);
+      __syncthreads();
     }
-    awrite((c + 1) & 1);
-    __syncthreads();
   }
 
-  // register i holds tile row (i & 3) + 8 * (i >> 2) + 4h of column n
+  // register i holds tile row (i & 3) + 8 * (i >> 2) + 4h of column n. The
+  // scales are powers of two: applying them to the fp32 sums is exact.
   const long n = n0 + r;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int pr = pair_s[(i & 3) + 8 * (i >> 2) + 4 * h];
     if (pr < 0) continue;
     if constexpr (GU) {
-      const float g = acc0[i];
+      const float g = acc0[i] * sc0;
       const float s = g / (1.f + expf(-g));
-      const __bf16 b = (__bf16)(s * acc1[i]);
+      const __bf16 b = (__bf16)(s * (acc1[i] * sc1));
       hout[(size_t)pr * N + n] = __builtin_bit_cast(u16, b);
     } else {
-      part[((size_t)blockIdx.z * npairs + pr) * N + n] = acc0[i] * route_w[pr];
+      part[((size_t)blockIdx.z * npairs + pr) * N + n] =
+          acc0[i] * sc0 * route_w[pr];
     }
   }
 }
@@ -348,6 +436,34 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
   *reinterpret_cast<vec2w*>(out + (size_t)t * D + d) = o;
 }
 
+// The two routed GEMMs for weights of type WT. The gate/up GEMM takes all of
+// K (a step is 64 k of bf16, 128 k of e4m3); the down GEMM's S slices are
+// counted in 128-k tiles for both types.
+template <typename WT>
+void launch_gemms(const void* x, long x_stride, const void* w_gate_up,
+                  const void* w_down, const void* gate_up_scale,
+                  const void* down_scale, const void* weights,
+                  const void* expert_count, const void* expert_rows, void* h,
+                  void* part, int T, int D, int I, int E, int top_k, int S,
+                  hipStream_t stream) {
+  const int np = T * top_k;
+  hipLaunchKernelGGL((moe_gemm_kernel<true, WT>),
+                     dim3((unsigned)(I / MOE_BN), (unsigned)E, 1),
+                     dim3(MOE_THREADS), 0, stream, (const u16*)x, x_stride, T,
+                     (const WT*)w_gate_up, (const float*)gate_up_scale,
+                     (const int*)expert_count, (const int*)expert_rows,
+                     (const float*)nullptr, (u16*)h, (float*)nullptr, top_k, I,
+                     D, np, D / (128 / (int)sizeof(WT)));
+  const int kt = I / 128;
+  hipLaunchKernelGGL((moe_gemm_kernel<false, WT>),
+                     dim3((unsigned)(D / MOE_BN), (unsigned)E, (unsigned)S),
+                     dim3(MOE_THREADS), 0, stream, (const u16*)h, (long)I, np,
+                     (const WT*)w_down, (const float*)down_scale,
+                     (const int*)expert_count, (const int*)expert_rows,
+                     (const float*)weights, (u16*)nullptr, (float*)part, top_k,
+                     D, I, np, (kt + S - 1) / S);
+}
+
 }  // namespace
 
 extern "C" {
@@ -380,30 +496,26 @@ void kt_moe_route(const void* logits, int is_bf16, void* sel, void* weights,
 }
 
 // x: [T, D] bf16, row stride x_stride elements; w_gate_up: [E, 2I, D] and
-// w_down: [E, D, I] bf16 contiguous; weights, expert_count, expert_rows: as
-// kt_moe_route wrote them; h: [T, top_k, I] bf16 and part: [S, T, top_k, D]
-// fp32 scratch; out: [T, D] bf16. The binding has checked 1 <= T <= 32,
-// D % 128 == I % 128 == 0, both <= 2^16, 1 <= S <= 64 and the alignments.
+// w_down: [E, D, I] contiguous, bf16 or (fp8 != 0) e4m3 with the row scales
+// gate_up_scale [E, 2I] and down_scale [E, D] fp32 (not read otherwise);
+// weights, expert_count, expert_rows: as kt_moe_route wrote them;
+// h: [T, top_k, I] bf16 and part: [S, T, top_k, D] fp32 scratch; out: [T, D]
+// bf16. The binding has checked 1 <= T <= 32, D % 128 == I % 128 == 0, both
+// <= 2^16, 1 <= S <= 64 and the alignments.
 void kt_moe_mlp(const void* x, long x_stride, const void* w_gate_up,
                 const void* w_down, const void* weights,
                 const void* expert_count, const void* expert_rows, void* h,
                 void* part, void* out, int T, int D, int I, int E, int top_k,
-                int S, hipStream_t stream) {
-  const int np = T * top_k;
-  hipLaunchKernelGGL(moe_gemm_kernel<true>,
-                     dim3((unsigned)(I / MOE_BN), (unsigned)E, 1),
-                     dim3(MOE_THREADS), 0, stream, (const u16*)x, x_stride, T,
-                     (const u16*)w_gate_up, (const int*)expert_count,
-                     (const int*)expert_rows, (const float*)nullptr, (u16*)h,
-                     (float*)nullptr, top_k, I, D, np, D / 64);
-  const int kt = I / 128;
-  hipLaunchKernelGGL(moe_gemm_kernel<false>,
-                     dim3((unsigned)(D / MOE_BN), (unsigned)E, (unsigned)S),
-                     dim3(MOE_THREADS), 0, stream, (const u16*)h, (long)I, np,
-                     (const u16*)w_down, (const int*)expert_count,
-                     (const int*)expert_rows, (const float*)weights,
-                     (u16*)nullptr, (float*)part, top_k, D, I, np,
-                     (kt + S - 1) / S);
+                int S, int fp8, const void* gate_up_scale,
+                const void* down_scale, hipStream_t stream) {
+  if (fp8)
+    launch_gemms<unsigned char>(x, x_stride, w_gate_up, w_down, gate_up_scale,
+                                down_scale, weights, expert_count, expert_rows,
+                                h, part, T, D, I, E, top_k, S, stream);
+  else
+    launch_gemms<u16>(x, x_stride, w_gate_up, w_down, nullptr, nullptr,
+                      weights, expert_count, expert_rows, h, part, T, D, I, E,
+                      top_k, S, stream);
   const long n4 = (long)T * (D / 4);
   hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n4 + 255) / 256)),
                      dim3(256), 0, stream, (const float*)part, (u16*)out, T, D,

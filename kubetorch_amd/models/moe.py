@@ -18,7 +18,8 @@ FusedMoEMLP / fuse_moe are the single-rank inference form of the same
 block: the experts' weights stacked into two parameters and the whole MLP
 one ops.moe_mlp call, which at decode sizes (at most 32 tokens) runs the
 gfx950 routed-GEMM kernels without a host sync, so the serving engine keeps
-its captured decode graph.
+its captured decode graph, and above that (prefill, wide decode steps) the
+gfx950 grouped-GEMM kernels, again without a host sync.
 
 The reference ships no model code — this extends the
 flagship family the launchers run, and is the EP workload the SPMD
@@ -166,8 +167,9 @@ class FusedMoEMLP(nn.Module):
     (ops.quantize_weight_fp8 per expert); a dtype cast of the model then
     leaves them as they are, device moves apply."""
 
-    # Calls of more rows than this run ops.moe_mlp's composition, which syncs
-    # the host: the serving engine captures no decode graph above it.
+    # The rows of ops.moe_mlp's decode kernels. Calls of more rows run its
+    # grouped kernels (no host sync either); the serving engine still captures
+    # no decode graph above this.
     graph_max_rows = ops.MOE_MAX_ROWS
 
     def __init__(self, dim, intermediate, n_experts=8, top_k=2, device=None,

@@ -1699,7 +1699,7 @@ class LinearW8(torch.nn.Module):
 # ---------------------------------------------------------------------------
 # Routed expert MLP for decode (mixture of experts, top-k)
 # ---------------------------------------------------------------------------
-MOE_MAX_ROWS = 32          # the kernel's T; more tokens run the composition
+MOE_MAX_ROWS = 32          # the kernel's T; more tokens run the grouped kernels
 MOE_MAX_EXPERTS = 64
 MOE_MAX_TOP_K = 8
 MOE_DIM_MULTIPLE = 128
@@ -1786,6 +1786,50 @@ def _moe_kernel_ok(x, router_logits, w_gate_up, w_down, top_k,
                             and x2.stride(0) % 8 == 0)))
 
 
+MOE_GROUPED_MAX_ROWS = 4096   # tokens per launch of the grouped kernels
+MOE_GROUPED_TILE_ROWS = 64    # their M tile (MGG_BM in moe_grouped.hip)
+
+
+def _moe_grouped_kernel_ok(x, router_logits, w_gate_up, w_down, top_k,
+                           w_gate_up_scale=None, w_down_scale=None):
+    """What the grouped kernels take: _moe_kernel_ok's conditions with more
+    than 32 rows, and a row stride that keeps one launch's rows of x inside
+    2 GiB."""
+    E, D, I = w_down.shape
+    wdt = W8_DTYPE if w_gate_up_scale is not None else torch.bfloat16
+    if not (x.is_cuda and x.dtype == torch.bfloat16
+            and w_gate_up.dtype == wdt and w_down.dtype == wdt
+            and router_logits.dtype in (torch.bfloat16, torch.float32)
+            and E <= MOE_MAX_EXPERTS and top_k <= MOE_MAX_TOP_K
+            and D % MOE_DIM_MULTIPLE == 0 and I % MOE_DIM_MULTIPLE == 0
+            and 0 < D <= MOE_MAX_DIM and 0 < I <= MOE_MAX_DIM
+            and w_gate_up.is_contiguous() and w_down.is_contiguous()):
+        return False
+    if w_gate_up_scale is not None and not (
+            w_down_scale is not None and w_gate_up_scale.is_contiguous()
+            and w_down_scale.is_contiguous()):
+        return False
+    x2 = _w8_rows(x, D)
+    if x2 is None:
+        return False
+    return (x2.shape[0] > MOE_MAX_ROWS and x2.stride(1) == 1
+            and x2.data_ptr() % 16 == 0 and x2.stride(0) % 8 == 0
+            and 0 <= x2.stride(0) <= (1 << 29) // MOE_GROUPED_MAX_ROWS)
+
+
+def _moe_mlp_grouped(x2, logits2, w_gate_up, w_down, top_k, w_gate_up_scale,
+                     w_down_scale):
+    """The grouped kernels over consecutive chunks of MOE_GROUPED_MAX_ROWS
+    tokens: exact, a token's result does not depend on its batch, and the
+    number of chunks comes from the shapes alone."""
+    T, step = x2.shape[0], MOE_GROUPED_MAX_ROWS
+    outs = [_ext().moe_mlp_grouped(x2[t:t + step], logits2[t:t + step],
+                                   w_gate_up, w_down, top_k, w_gate_up_scale,
+                                   w_down_scale)
+            for t in range(0, T, step)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+
 def _moe_mlp_ref(x2, logits2, w_gate_up, w_down, top_k, w_gate_up_scale=None,
                  w_down_scale=None):
     """The composition: route, then per picked expert gather its tokens, run
@@ -1848,10 +1892,19 @@ def moe_mlp(x, router_logits, w_gate_up, w_down, top_k, num_splits=None,
     aligned rows runs the gfx950 kernels: four launches, no host sync
     (capturable in a graph), only the picked experts' weights are read, bit-
     identical run to run, a token's result independent of the other tokens in
-    the call. Any other valid input, the CPU included, runs a torch
-    composition that loops over the picked experts and syncs the host.
-    num_splits overrides the down GEMM's split-K factor (tests); the
-    composition ignores it."""
+    the call. The same inputs with more than 32 rows (a row stride of x up to
+    2^17) run the grouped GEMM kernels: routing, a counting sort of the
+    (token, slot) pairs by expert into 64-row tiles, the two GEMMs over the
+    tiles and the combine, five launches per MOE_GROUPED_MAX_ROWS tokens,
+    again with no host sync, capturable, reading only the picked experts'
+    weights, bit-identical run to run and a token's result independent of the
+    other tokens. The two kernel paths walk K in different orders, so a token
+    may differ in its last bits between a call of at most 32 rows and a
+    larger one; both meet the contract above. Any other valid input, the CPU
+    included, runs a torch composition that loops over the picked experts and
+    syncs the host. num_splits overrides the 32-row down GEMM's split-K
+    factor (tests); the grouped kernels, which do not split K, and the
+    composition ignore it."""
     fp8 = any(torch.is_tensor(w) and w.dtype in _FLOAT8_DTYPES
               for w in (w_gate_up, w_down)) \
         or w_gate_up_scale is not None or w_down_scale is not None
@@ -1913,6 +1966,12 @@ def moe_mlp(x, router_logits, w_gate_up, w_down, top_k, num_splits=None,
                              router_logits.reshape(-1, E).contiguous(),
                              w_gate_up, w_down, top_k, int(num_splits or 0),
                              w_gate_up_scale, w_down_scale)
+    elif _moe_grouped_kernel_ok(x, router_logits, w_gate_up, w_down, top_k,
+                                w_gate_up_scale, w_down_scale):
+        out = _moe_mlp_grouped(_w8_rows(x, D),
+                               router_logits.reshape(-1, E).contiguous(),
+                               w_gate_up, w_down, top_k, w_gate_up_scale,
+                               w_down_scale)
     else:
         out = _moe_mlp_ref(x.reshape(-1, D), router_logits.reshape(-1, E),
                            w_gate_up, w_down, top_k, w_gate_up_scale,

@@ -20,7 +20,8 @@ MODULES = {
     "_hip_ops": ["kernels.hip", "attention.hip", "attention_ck.hip",
                  "attention_ck_bwd.hip", "paged_attention.hip",
                  "paged_prefill.hip", "sampler.hip", "logprobs.hip",
-                 "linear_w8.hip", "moe.hip", "bindings.cpp"],
+                 "linear_w8.hip", "moe.hip", "moe_grouped.hip",
+                 "bindings.cpp"],
     "_hip_spill": ["spill.cpp"],
 }
 SO_PATH = os.path.join(OPS_DIR, "_hip_ops.so")  # primary (back-compat)
@@ -93,8 +94,8 @@ def _build_module(name, sources, verbose, force):
             # disable; these TUs have no torch headers -> drop the guards.
             src_flags = [f for f in flags
                          if not f.startswith("-D__HIP_NO_HALF")]
-        if src == "moe.hip":
-            # no packed fp32 arithmetic (v_pk_*_f32) in this file's code
+        if src in ("moe.hip", "moe_grouped.hip"):
+            # no packed fp32 arithmetic (v_pk_*_f32) in these files' code
             src_flags = flags + ["-Xclang", "-target-feature",
                                  "-Xclang", "-packed-fp32-ops"]
         cmd = [hipcc, "-c", os.path.join(HIP_DIR, src), "-o", obj] + src_flags

@@ -907,17 +907,18 @@ std::vector<at::Tensor> moe_route(const at::Tensor& logits, int64_t top_k) {
   return {sel, weights, count, rows};
 }
 
-at::Tensor moe_mlp(const at::Tensor& x, const at::Tensor& logits,
-                   const at::Tensor& w_gate_up, const at::Tensor& w_down,
-                   int64_t top_k, int64_t num_splits,
-                   const c10::optional<at::Tensor>& w_gate_up_scale,
-                   const c10::optional<at::Tensor>& w_down_scale) {
+// The argument checks moe_mlp and moe_mlp_grouped share; the number of rows
+// and x's row stride are the caller's to bound.
+void check_moe_mlp_args(const at::Tensor& x, const at::Tensor& logits,
+                        const at::Tensor& w_gate_up, const at::Tensor& w_down,
+                        const c10::optional<at::Tensor>& w_gate_up_scale,
+                        const c10::optional<at::Tensor>& w_down_scale) {
   // x: [T, D] bf16, last dim contiguous, row base and stride 16 B aligned;
   // w_gate_up: [E, 2I, D] and w_down: [E, D, I] contiguous, both bf16 with
   // no scales or both e4m3 with the fp32 row scales [E, 2I] and [E, D]; D
   // and I multiples of 128 up to 2^16 (ops.moe_mlp sends everything else to
-  // the composition). num_splits 0 is the kernel's own choice from the
-  // shapes. The scale values are not looked at here (a device sync).
+  // the composition). The scale values are not looked at here (a device
+  // sync).
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
               "x must be [T, D] bf16 on GPU");
   const int64_t T = x.size(0), D = x.size(1);
@@ -954,8 +955,21 @@ at::Tensor moe_mlp(const at::Tensor& x, const at::Tensor& logits,
                     sd.is_contiguous() && sd.device() == x.device(),
                 "w_down_scale must be [E, D] fp32, contiguous, on x's device");
   }
-  const int64_t xs = T > 1 ? x.stride(0) : D;
   TORCH_CHECK(x.stride(1) == 1, "x's last dim must be contiguous");
+}
+
+at::Tensor moe_mlp(const at::Tensor& x, const at::Tensor& logits,
+                   const at::Tensor& w_gate_up, const at::Tensor& w_down,
+                   int64_t top_k, int64_t num_splits,
+                   const c10::optional<at::Tensor>& w_gate_up_scale,
+                   const c10::optional<at::Tensor>& w_down_scale) {
+  // num_splits 0 is the kernel's own choice from the shapes.
+  check_moe_mlp_args(x, logits, w_gate_up, w_down, w_gate_up_scale,
+                     w_down_scale);
+  const int64_t T = x.size(0), D = x.size(1);
+  const int64_t E = w_gate_up.size(0), I = w_down.size(2);
+  const bool fp8 = w_gate_up.scalar_type() == at::kFloat8_e4m3fn;
+  const int64_t xs = T > 1 ? x.stride(0) : D;
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
                   xs >= 0 && xs % 8 == 0 && xs <= (1 << 24),
               "x rows must be 16-byte aligned, with a stride up to 2^24");
@@ -974,6 +988,57 @@ at::Tensor moe_mlp(const at::Tensor& x, const at::Tensor& logits,
              (int)I, (int)E, (int)top_k, S, fp8 ? 1 : 0,
              scale_ptr(w_gate_up_scale), scale_ptr(w_down_scale),
              cur_stream(x));
+  return out;
+}
+
+// The same MLP for 1 <= T <= 4096 rows through the grouped GEMM kernels
+// (ops.moe_mlp sends more than 32 rows here, in chunks): routing, alignment,
+// the two grouped GEMMs and the combine on the current stream, no host sync.
+at::Tensor moe_mlp_grouped(const at::Tensor& x, const at::Tensor& logits,
+                           const at::Tensor& w_gate_up,
+                           const at::Tensor& w_down, int64_t top_k,
+                           const c10::optional<at::Tensor>& w_gate_up_scale,
+                           const c10::optional<at::Tensor>& w_down_scale) {
+  check_moe_mlp_args(x, logits, w_gate_up, w_down, w_gate_up_scale,
+                     w_down_scale);
+  const int64_t T = x.size(0), D = x.size(1);
+  const int64_t E = w_gate_up.size(0), I = w_down.size(2);
+  const bool fp8 = w_gate_up.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(T >= 1 && T <= 4096, "T must be in [1, 4096], got ", T);
+  TORCH_CHECK(E >= 1 && E <= 64, "E must be in [1, 64], got ", E);
+  TORCH_CHECK(top_k >= 1 && top_k <= E && top_k <= 8,
+              "top_k must be in [1, min(E, 8)], got ", top_k);
+  TORCH_CHECK(logits.is_contiguous() &&
+                  (logits.scalar_type() == at::kBFloat16 ||
+                   logits.scalar_type() == at::kFloat),
+              "router_logits must be bf16 or fp32, contiguous");
+  const int64_t xs = T > 1 ? x.stride(0) : D;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+                  xs >= 0 && xs % 8 == 0 &&
+                  ((T - 1) * xs + D) * 2 < (int64_t(1) << 31),
+              "x rows must be 16-byte aligned and span less than 2 GiB");
+  c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  const int64_t M = kt_moe_grouped_max_tiles(T, (int)E, (int)top_k);
+  const int64_t rows = M * kt_moe_grouped_tile_rows();
+  auto i32 = x.options().dtype(at::kInt);
+  auto f32 = x.options().dtype(at::kFloat);
+  auto sel = at::empty({T, top_k}, i32);
+  auto weights = at::empty({T, top_k}, f32);
+  // expert_count [E], n_tiles [1], tile_expert [M], tile_row0 [M],
+  // sorted_pairs [rows] in one allocation
+  auto table = at::empty({E + 1 + 2 * M + rows}, i32);
+  int* tb = table.data_ptr<int>();
+  auto h = at::empty({rows, I}, x.options());
+  auto part = at::empty({T, top_k, D}, f32);
+  auto out = at::empty({T, D}, x.options());
+  kt_moe_grouped_mlp(x.data_ptr(), (long)xs, logits.data_ptr(),
+                     logits.scalar_type() == at::kBFloat16,
+                     w_gate_up.data_ptr(), w_down.data_ptr(), sel.data_ptr(),
+                     weights.data_ptr(), tb, tb + E + 1 + 2 * M, tb + E + 1,
+                     tb + E + 1 + M, tb + E, h.data_ptr(), part.data_ptr(),
+                     out.data_ptr(), (int)T, (int)D, (int)I, (int)E,
+                     (int)top_k, fp8 ? 1 : 0, scale_ptr(w_gate_up_scale),
+                     scale_ptr(w_down_scale), cur_stream(x));
   return out;
 }
 
@@ -1046,6 +1111,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           pybind11::arg("top_k"), pybind11::arg("num_splits"),
           pybind11::arg("w_gate_up_scale") = pybind11::none(),
           pybind11::arg("w_down_scale") = pybind11::none());
+  mod.def("moe_mlp_grouped", &moe_mlp_grouped,
+          "Routed expert SwiGLU MLP of T <= 4096 rows of bf16 x -> [T, D], "
+          "grouped GEMM kernels",
+          pybind11::arg("x"), pybind11::arg("router_logits"),
+          pybind11::arg("w_gate_up"), pybind11::arg("w_down"),
+          pybind11::arg("top_k"),
+          pybind11::arg("w_gate_up_scale") = pybind11::none(),
+          pybind11::arg("w_down_scale") = pybind11::none());
+  mod.def("moe_grouped_tile_rows", &kt_moe_grouped_tile_rows,
+          "Rows of the grouped GEMM's M tile");
   mod.def("moe_down_splits", &moe_down_splits,
           "The split-K factor moe_mlp's down GEMM chooses for the shapes");
 }

@@ -128,5 +128,21 @@ void kt_moe_mlp(const void* x, long x_stride, const void* w_gate_up,
                 void* part, void* out, int T, int D, int I, int E, int top_k,
                 int S, int fp8, const void* gate_up_scale,
                 const void* down_scale, hipStream_t stream);
+// out [T, D] bf16 = the sum over s, then j, of part [S, T, top_k, D] fp32
+void kt_moe_combine(const void* part, void* out, int T, int D, int top_k,
+                    int S, hipStream_t stream);
+
+// moe_grouped.hip: the same MLP for more than 32 rows. The scratch arrays are
+// sized by kt_moe_grouped_max_tiles (tiles of kt_moe_grouped_tile_rows rows).
+int kt_moe_grouped_tile_rows(void);
+int kt_moe_grouped_max_tiles(long T, int E, int top_k);
+void kt_moe_grouped_mlp(const void* x, long x_stride, const void* logits,
+                        int is_bf16, const void* w_gate_up,
+                        const void* w_down, void* sel, void* weights,
+                        void* expert_count, void* sorted_pairs,
+                        void* tile_expert, void* tile_row0, void* n_tiles,
+                        void* h, void* part, void* out, int T, int D, int I,
+                        int E, int top_k, int fp8, const void* gate_up_scale,
+                        const void* down_scale, hipStream_t stream);
 
 }  // extern "C"

@@ -71,13 +71,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include "device_common.h"
 #include "kt_launchers.h"
+#include "moe_common.h"
 
 #define MOE_THREADS 256
 #define MOE_BN 128                  // output columns per workgroup
 #define MOE_ROWS 32                 // rows of an expert's tile (max T)
-#define MOE_MAX_E 64
 
 namespace {
 
@@ -85,24 +84,12 @@ namespace {
 // Routing
 // ---------------------------------------------------------------------------
 
-// exp(v - m) for v <= m in fp32. v == m is 1 (infinities included); the
-// rounding error of v - m is recovered (TwoSum) and applied to first order,
-// so the result is as accurate as expf itself for any spread of the logits.
-__device__ __forceinline__ float exp_diff(float v, float m) {
-  if (v == m) return 1.f;
-  const float d = v - m;
-  if (d == -INFINITY) return 0.f;
-  const float b = -m;
-  const float bb = d - v;
-  const float err = (v - (d - bb)) + (b - bb);
-  return expf(d) * (1.f + err);
-}
-
 // One workgroup. Pass 1, a wave per token and a lane per expert: rank the
 // logits (descending, equal logits lowest index first, NaN as -inf), write
-// the k best and their softmax. Pass 2, a wave per expert and a lane per
-// token: a ballot of the tokens that picked the expert gives its count and,
-// by prefix count, each pair's row in token order.
+// the k best and their softmax (moe_route_token, shared with the grouped
+// kernels). Pass 2, a wave per expert and a lane per token: a ballot of the
+// tokens that picked the expert gives its count and, by prefix count, each
+// pair's row in token order.
 __global__ __launch_bounds__(MOE_THREADS) void moe_route_kernel(
     const void* __restrict__ logits, int is_bf16, int* __restrict__ sel,
     float* __restrict__ weights, int* __restrict__ expert_count,
@@ -112,31 +99,9 @@ __global__ __launch_bounds__(MOE_THREADS) void moe_route_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   for (int t = wave; t < T; t += MOE_THREADS / 64) {  // wave-uniform
-    float v = -INFINITY;
-    if (lane < E) {
-      v = is_bf16 ? bf2f(((const u16*)logits)[t * E + lane])
-                  : ((const float*)logits)[t * E + lane];
-      if (v != v) v = -INFINITY;
-    }
-    int rank = 0;
-    for (int o = 0; o < E; ++o) {
-      const float vo = __shfl(v, o);
-      rank += (vo > v || (vo == v && o < lane)) ? 1 : 0;
-    }
-    const bool picked = lane < E && rank < top_k;
-    // the picked logits in slot order: every lane sums them the same way
-    float m = 0.f, sum = 0.f;
-    for (int j = 0; j < top_k; ++j) {
-      const unsigned long long b = __ballot(lane < E && rank == j);
-      const float vj = __shfl(v, __ffsll((long long)b) - 1);
-      if (j == 0) m = vj;
-      sum += exp_diff(vj, m);
-    }
-    if (picked) {
-      sel[t * top_k + rank] = lane;
-      weights[t * top_k + rank] = exp_diff(v, m) / sum;
-    }
-    if (lane < E) slot_of[t][lane] = picked ? (signed char)rank : (signed char)-1;
+    const int slot =
+        moe_route_token(logits, is_bf16, t, E, top_k, lane, sel, weights);
+    if (lane < E) slot_of[t][lane] = (signed char)slot;
   }
   __syncthreads();
 
@@ -157,23 +122,8 @@ struct WStep {
   vec4w v[8];
 };
 
-// Raw buffer loads: a lane whose offset is at or past the resource's size
-// gets zeros and makes no memory request, so empty rows, the tail of a K
-// slice and the prefetch past its end need no branch.
-#define MOE_RSRC_FLAGS 0x00020000  // gfx9 raw buffer, 32-bit data format
-#define MOE_OOB 0x80000000u        // every resource here is < 2 GiB
-
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-__device__ __forceinline__ vec4w buf_load(rsrc_t rs, unsigned off) {
-  return __builtin_bit_cast(
-      vec4w, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0));
-}
-
-__device__ __forceinline__ bf16x8 frag(vec4w v) {
-  return __builtin_bit_cast(bf16x8, v);
-}
-
+// The raw buffer loads (buf_load, MOE_OOB) are moe_common.h's.
+//
 // GU: a = x [a_rows, K] (row stride a_stride), w = w_gate_up [E, 2N, K],
 //     writes h [npairs, N].
 // !GU: a = h [npairs, K], w = w_down [E, N, K], writes part [S, npairs, N]
@@ -516,6 +466,12 @@ void kt_moe_mlp(const void* x, long x_stride, const void* w_gate_up,
     launch_gemms<u16>(x, x_stride, w_gate_up, w_down, nullptr, nullptr,
                       weights, expert_count, expert_rows, h, part, T, D, I, E,
                       top_k, S, stream);
+  kt_moe_combine(part, out, T, D, top_k, S, stream);
+}
+
+// part: [S, T, top_k, D] fp32, every slab written; out: [T, D] bf16.
+void kt_moe_combine(const void* part, void* out, int T, int D, int top_k,
+                    int S, hipStream_t stream) {
   const long n4 = (long)T * (D / 4);
   hipLaunchKernelGGL(moe_combine_kernel, dim3((unsigned)((n4 + 255) / 256)),
                      dim3(256), 0, stream, (const float*)part, (u16*)out, T, D,

@@ -1494,7 +1494,11 @@ class Linear(torch.nn.Linear):
 W8_DTYPE = torch.float8_e4m3fn
 W8_MAX = 448.0
 W8_SCALE_EXP = 40          # scales lie in [2^-40, 2^40]
-W8_MAX_ROWS = 32           # the kernel's M; more rows run the composition
+W8_MAX_ROWS = 32           # the skinny kernel's M
+# The 64-row-tile kernel's M; more rows run the composition. Measured: the
+# largest M at which the kernel beats the composition at all five 8B shapes
+# (profiles/linear_w8_wide.md). At most 4096: the binding bounds the grid.
+W8_WIDE_MAX_ROWS = 512
 W8_K_MULTIPLE = 128
 
 
@@ -1596,6 +1600,26 @@ def _linear_w8_kernel_ok(x, weight_q, weight_scale):
                             and x2.stride(0) % 8 == 0)))
 
 
+def _linear_w8_wide_ok(x, weight_q, weight_scale):
+    """What the 64-row-tile kernel takes: the operands of
+    _linear_w8_kernel_ok with W8_MAX_ROWS < M <= W8_WIDE_MAX_ROWS, all of x
+    inside 2 GiB (it is one buffer resource) and N <= 2^18 (the grid)."""
+    K = weight_q.shape[1]
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and K >= W8_K_MULTIPLE
+            and K % W8_K_MULTIPLE == 0 and K <= 1 << 24
+            and 1 <= weight_q.shape[0] <= 1 << 18
+            and weight_q.is_contiguous()):
+        return False
+    x2 = _w8_rows(x, K)
+    if x2 is None:
+        return False
+    M = x2.shape[0]
+    return (W8_MAX_ROWS < M <= W8_WIDE_MAX_ROWS and x2.stride(1) == 1
+            and x2.data_ptr() % 16 == 0
+            and 0 <= x2.stride(0) <= 1 << 24 and x2.stride(0) % 8 == 0
+            and (M - 1) * x2.stride(0) + K < 1 << 30)
+
+
 def linear_w8_splits(out_features, in_features):
     """The split-K factor the kernel chooses for an [out, in] weight: a
     function of the shape alone, never of the batch or of device data."""
@@ -1609,13 +1633,17 @@ def linear_w8(x, weight_q, weight_scale, num_splits=None):
     at the end. x is [..., K]; the leading dimensions flatten to M rows.
     Inference-only: x must not require grad while grad is enabled.
 
-    bf16 GPU x with 1 <= M <= 32, K % 128 == 0, a contiguous last dim,
-    16-byte aligned rows and a contiguous weight_q runs the gfx950 kernel
-    (weights streamed once as fp8, bit-identical run to run, a row's result
-    independent of the other rows in the call). Any other valid input, the
-    CPU included, runs F.linear(x, dequantize_weight_fp8(q, scale, x.dtype)),
-    whose temporary comes from the caching allocator. num_splits overrides
-    the kernel's split-K factor (tests); the composition ignores it.
+    bf16 GPU x with K % 128 == 0, a contiguous last dim, 16-byte aligned
+    rows and a contiguous weight_q runs a gfx950 kernel: the skinny one for
+    1 <= M <= 32, the 64-row-tile one for 32 < M <= W8_WIDE_MAX_ROWS (x
+    inside 2 GiB, N <= 2^18). Both stream the weights as fp8, are
+    bit-identical run to run and make a row's result independent of the
+    other rows in the call; the two kernels sum k in the same order, so a
+    row's bits are the same from either. Any other valid input, the CPU and
+    more rows included, runs F.linear(x, dequantize_weight_fp8(q, scale,
+    x.dtype)), whose temporary comes from the caching allocator. num_splits
+    overrides the kernels' split-K factor (tests); the composition ignores
+    it.
 
     Wrong dtypes (weight_q not float8_e4m3fn, weight_scale not fp32), wrong
     shapes and mismatched devices raise. Scale values are checked on the CPU
@@ -1634,9 +1662,14 @@ def linear_w8(x, weight_q, weight_scale, num_splits=None):
         raise ValueError("num_splits must be in [1, 64]")
     if torch.is_grad_enabled() and x.requires_grad:
         raise RuntimeError("linear_w8 is inference-only: x requires grad")
+    kernel = None
     if _linear_w8_kernel_ok(x, weight_q, weight_scale):
-        y = _ext().linear_w8(_w8_rows(x, K), weight_q,
-                             weight_scale.contiguous(), int(num_splits or 0))
+        kernel = _ext().linear_w8
+    elif _linear_w8_wide_ok(x, weight_q, weight_scale):
+        kernel = _ext().linear_w8_wide
+    if kernel is not None:
+        y = kernel(_w8_rows(x, K), weight_q, weight_scale.contiguous(),
+                   int(num_splits or 0))
         return y.view(*x.shape[:-1], N)
     return torch.nn.functional.linear(
         x, dequantize_weight_fp8(weight_q, weight_scale, x.dtype))

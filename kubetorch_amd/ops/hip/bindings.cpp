@@ -834,13 +834,15 @@ std::vector<at::Tensor> token_logprobs(const at::Tensor& logits,
   return {logprob, rank, top_ids, top_lp};
 }
 
-at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq,
-                     const at::Tensor& scale, int64_t num_splits) {
-  // x: [M, K] bf16, 1 <= M <= 32, last dim contiguous, row base and stride
-  // 16 B aligned; wq: [N, K] e4m3 contiguous, K % 128 == 0; scale: [N] fp32
-  // (ops.linear_w8 sends everything else to the composition). num_splits 0
-  // is the kernel's own choice from (N, K). The scale values are not looked
-  // at here (that would be a device sync).
+at::Tensor linear_w8_rows(const at::Tensor& x, const at::Tensor& wq,
+                          const at::Tensor& scale, int64_t num_splits,
+                          bool wide) {
+  // x: [M, K] bf16, 1 <= M <= 32 (wide: M >= 33, all of x below 2 GiB), last
+  // dim contiguous, row base and stride 16 B aligned; wq: [N, K] e4m3
+  // contiguous, K % 128 == 0; scale: [N] fp32 (ops.linear_w8 sends
+  // everything else to the composition). num_splits 0 is the kernel's own
+  // choice from (N, K). The scale values are not looked at here (that would
+  // be a device sync).
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2,
               "x must be [M, K] bf16 on GPU");
   TORCH_CHECK(wq.is_cuda() && wq.device() == x.device() &&
@@ -852,7 +854,8 @@ at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq,
   TORCH_CHECK(wq.size(1) == K, "x's last dim must be weight_q's K");
   check_vec(scale, at::kFloat, N, x.device(),
             "weight_scale must be [N] fp32, contiguous, on x's device");
-  TORCH_CHECK(M >= 1 && M <= 32, "M must be in [1, 32], got ", M);
+  TORCH_CHECK(wide ? M >= 33 && M <= (1 << 20) : M >= 1 && M <= 32,
+              "M must be in ", wide ? "[33, 2^20]" : "[1, 32]", ", got ", M);
   TORCH_CHECK(K >= 128 && K % 128 == 0 && K <= (1 << 24),
               "K must be a multiple of 128 up to 2^24, got ", K);
   TORCH_CHECK(N >= 1 && N <= (1 << 30), "N must be in [1, 2^30], got ", N);
@@ -864,14 +867,31 @@ at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq,
   TORCH_CHECK(num_splits >= 0 && num_splits <= 64,
               "num_splits must be in [0, 64], got ", num_splits);
   const int S = num_splits > 0 ? (int)num_splits : kt_linear_w8_plan(N, K);
+  if (wide) {
+    TORCH_CHECK(((M - 1) * xs + K) * 2 < (int64_t(1) << 31),
+                "x must span less than 2 GiB");
+    TORCH_CHECK(((M + 63) / 64) * ((N + 127) / 128) * S <= (1 << 23),
+                "too many workgroups: M ", M, ", N ", N, ", splits ", S);
+  }
   c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
   auto y = at::empty({M, N}, x.options());
   at::Tensor part;
   if (S > 1) part = at::empty({S, M, N}, x.options().dtype(at::kFloat));
-  kt_linear_w8(x.data_ptr(), (long)xs, wq.data_ptr(), scale.data_ptr(),
-               y.data_ptr(), S > 1 ? part.data_ptr() : nullptr, (int)M, (int)N,
-               (int)K, S, cur_stream(x));
+  (wide ? kt_linear_w8_wide : kt_linear_w8)(
+      x.data_ptr(), (long)xs, wq.data_ptr(), scale.data_ptr(), y.data_ptr(),
+      S > 1 ? part.data_ptr() : nullptr, (int)M, (int)N, (int)K, S,
+      cur_stream(x));
   return y;
+}
+
+at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq,
+                     const at::Tensor& scale, int64_t num_splits) {
+  return linear_w8_rows(x, wq, scale, num_splits, false);
+}
+
+at::Tensor linear_w8_wide(const at::Tensor& x, const at::Tensor& wq,
+                          const at::Tensor& scale, int64_t num_splits) {
+  return linear_w8_rows(x, wq, scale, num_splits, true);
 }
 
 int64_t linear_w8_splits(int64_t N, int64_t K) {
@@ -1100,6 +1120,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "Per-row log-probability and rank of a token, and the top_n tokens");
   mod.def("linear_w8", &linear_w8,
           "y = x @ (e4m3 weight * scale)^T for M <= 32 rows of bf16 x");
+  mod.def("linear_w8_wide", &linear_w8_wide,
+          "The same for M >= 33 rows: 64-row tiles");
   mod.def("linear_w8_splits", &linear_w8_splits,
           "The split-K factor linear_w8 chooses for an [N, K] weight");
   mod.def("moe_route", &moe_route,

@@ -113,6 +113,10 @@ int kt_linear_w8_plan(long N, long K);
 void kt_linear_w8(const void* x, long x_stride, const void* wq,
                   const void* scale, void* y, void* part, int M, int N, int K,
                   int S, hipStream_t stream);
+// more than 32 rows: 64-row tiles, the same plan and reduce
+void kt_linear_w8_wide(const void* x, long x_stride, const void* wq,
+                       const void* scale, void* y, void* part, int M, int N,
+                       int K, int S, hipStream_t stream);
 
 // moe.hip. kt_moe_route writes the routing table that kt_moe_mlp reads.
 // fp8 != 0: the expert weights are e4m3 and the two scale arguments are

@@ -33,6 +33,9 @@
 // Safety: columns n >= N read row N-1 again and are not stored; an empty K
 // slice writes zeros. Every index that scales with N*K is 64-bit.
 //
+// linear_w8_wide_kernel, further down, is the same linear for M >= 33: 64 x
+// rows per workgroup, the same weight stream, K order, plan and reduce.
+//
 // No torch headers here; kt_launchers.h declares the extern "C" launchers.
 
 #include <hip/hip_runtime.h>
@@ -193,6 +196,156 @@ __global__ __launch_bounds__(LW_THREADS, 2) void linear_w8_kernel(
   }
 }
 
+// More than 32 rows. A workgroup owns (64 x rows, 128 output columns, K
+// slice): the weight stream, the K permutation and the epilogue are those of
+// the kernel above, but every B fragment feeds two MFMAs, one per 32-row
+// block, and the accumulator is two f32x16. The 64 x rows go through LDS one
+// 128-k tile at a time (256 B per row, 16 B per thread and row, four rows per
+// thread), double buffered, one barrier per tile; the weight ring holds the
+// tile in use and three in flight. blockIdx.x = column tile * m_tiles + row
+// tile: the workgroups that stream the same 128 weight rows are dispatched
+// together and all but the first find them in L2. Each x row is summed over
+// k in the same order wherever it sits in the call, so its bits depend on the
+// row, the weight and S alone.
+#define LWW_BM 64                  // x rows per workgroup
+#define LWW_LDX (LW_KT * 2 + 16)   // LDS row stride in bytes, 16 B pad
+#define LWW_RING 4                 // weight tiles in registers
+
+__global__ __launch_bounds__(LW_THREADS, 2) void linear_w8_wide_kernel(
+    const u16* __restrict__ x, long x_stride,
+    const unsigned char* __restrict__ wq, const float* __restrict__ scale,
+    u16* __restrict__ y, float* __restrict__ part, int M, int N, int K,
+    int tiles_per_split, int m_tiles) {
+  __shared__ __attribute__((aligned(16))) unsigned char
+      xs[2 * LWW_BM * LWW_LDX];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31;  // MFMA row/column index of this lane
+  const int h = lane >> 5;  // lane half
+  const int m0 = (int)(blockIdx.x % (unsigned)m_tiles) * LWW_BM;
+  const long cb = (long)(blockIdx.x / (unsigned)m_tiles);
+
+  // this workgroup's K slice, in tiles (block-uniform)
+  const int t0 = (int)blockIdx.y * tiles_per_split;
+  int nt = K / LW_KT - t0;
+  nt = nt > tiles_per_split ? tiles_per_split : nt;
+  nt = nt < 0 ? 0 : nt;
+  const size_t k0 = (size_t)(nt > 0 ? t0 : 0) * LW_KT;  // inside the row
+
+  // wq: the wave's 32 rows from column k0 on, as in the kernel above
+  const long n0 = cb * LW_BN + wave * 32;  // wave-uniform
+  const long nb = n0 < N ? n0 : (long)N - 1;
+  const long n = n0 + r;
+  const long nrows = (long)N - nb < 32 ? (long)N - nb : 32;
+  const rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<unsigned char*>(wq) + (size_t)nb * K + k0, 0,
+      (int)((nrows - 1) * K + (K - (long)k0)), LW_RSRC_FLAGS);
+  const unsigned woff =
+      (unsigned)((r < nrows ? r : nrows - 1) * (long)K) + 16 * h;
+  auto wtile = [&](int t) {  // tile t of the slice, zeros past its end
+    return load_tile(wrs, t < nt ? woff + (unsigned)t * LW_KT : LW_OOB);
+  };
+
+  // x staging: thread -> 16 B piece p of tile rows (tid >> 4) + 16i. One
+  // resource spans all of x from column k0 on (the binding keeps it below
+  // 2 GiB); rows >= M and tiles past the slice come back as zeros.
+  const int p = tid & 15;
+  const int row0 = tid >> 4;
+  const rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<u16*>(x) + k0, 0,
+      (int)(((long)(M - 1) * x_stride + (K - (long)k0)) * 2), LW_RSRC_FLAGS);
+  unsigned xbase[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long row = m0 + row0 + 16 * i;
+    xbase[i] = row < M ? (unsigned)((row * x_stride + p * 8) * 2) : LW_OOB;
+  }
+  vec4w xr[4];
+  auto xfetch = [&](int t) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      xr[i] = buf_load(xrs, t < nt && xbase[i] != LW_OOB
+                                ? xbase[i] + (unsigned)t * (LW_KT * 2)
+                                : LW_OOB);
+  };
+  auto xwrite = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      *reinterpret_cast<vec4w*>(
+          &xs[(buf * LWW_BM + row0 + 16 * i) * LWW_LDX + p * 16]) = xr[i];
+  };
+
+  f32x16 acc[2];  // [row block]
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[mb][i] = 0.f;
+
+  auto compute = [&](int buf, const WTile& w) {
+    const unsigned char* xb = &xs[(buf * LWW_BM + r) * LWW_LDX + 32 * h];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bf16x8 b0 = frag_fp8(w.v[u][0], w.v[u][1]);
+      const bf16x8 b1 = frag_fp8(w.v[u][2], w.v[u][3]);
+#pragma unroll
+      for (int mb = 0; mb < 2; ++mb) {
+        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(
+            xb + mb * 32 * LWW_LDX + 64 * u);
+        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(
+            xb + mb * 32 * LWW_LDX + 64 * u + 16);
+        acc[mb] =
+            __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[mb], 0, 0, 0);
+        acc[mb] =
+            __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[mb], 0, 0, 0);
+      }
+    }
+  };
+
+  // weight ring: tile tt is in wr[tt % RING], the next RING - 1 in flight
+  xfetch(0);
+  WTile wr[LWW_RING];
+#pragma unroll
+  for (int i = 0; i + 1 < LWW_RING; ++i) wr[i] = wtile(i);
+  xwrite(0);
+  __syncthreads();
+
+  for (int t = 0; t < nt; t += LWW_RING) {  // block-uniform trip count
+#pragma unroll
+    for (int i = 0; i < LWW_RING; ++i) {
+      const int tt = t + i;
+      if (tt >= nt) break;
+      xfetch(tt + 1);
+      wr[(i + LWW_RING - 1) % LWW_RING] = wtile(tt + LWW_RING - 1);
+      compute(i & 1, wr[i]);  // tt & 1: t is a multiple of the even RING
+      xwrite((i + 1) & 1);
+      __syncthreads();
+    }
+  }
+
+  if (n >= N) return;
+  const float sc = scale[n];
+  // register i of block mb holds x row m0 + 32 mb + (i & 3) + 8 * (i >> 2)
+  // + 4h of column n
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int m = m0 + 32 * mb + (i & 3) + 8 * (i >> 2) + 4 * h;
+      if (m < M) {
+        const float v = acc[mb][i] * sc;
+        if (part != nullptr) {
+          part[((size_t)blockIdx.y * M + m) * N + n] = v;
+        } else {
+          const __bf16 b = (__bf16)v;
+          y[(size_t)m * N + n] = __builtin_bit_cast(u16, b);
+        }
+      }
+    }
+  }
+}
+
 // y[i] = bf16(part[0][i] + part[1][i] + ... ), slabs of MN floats, in order
 __global__ __launch_bounds__(256) void linear_w8_reduce(
     const float* __restrict__ part, u16* __restrict__ y, long MN, int S) {
@@ -202,6 +355,12 @@ __global__ __launch_bounds__(256) void linear_w8_reduce(
   for (int s = 1; s < S; ++s) a += part[(size_t)s * MN + i];
   const __bf16 b = (__bf16)a;
   y[i] = __builtin_bit_cast(u16, b);
+}
+
+void launch_reduce(const void* part, void* y, long MN, int S,
+                   hipStream_t stream) {
+  hipLaunchKernelGGL(linear_w8_reduce, dim3((unsigned)((MN + 255) / 256)),
+                     dim3(256), 0, stream, (const float*)part, (u16*)y, MN, S);
 }
 
 }  // namespace
@@ -236,12 +395,25 @@ void kt_linear_w8(const void* x, long x_stride, const void* wq,
                      (const u16*)x, x_stride, (const unsigned char*)wq,
                      (const float*)scale, (u16*)y,
                      S > 1 ? (float*)part : (float*)nullptr, M, N, K, tps);
-  if (S > 1) {
-    const long MN = (long)M * N;
-    hipLaunchKernelGGL(linear_w8_reduce, dim3((unsigned)((MN + 255) / 256)),
-                       dim3(256), 0, stream, (const float*)part, (u16*)y, MN,
-                       S);
-  }
+  if (S > 1) launch_reduce(part, y, (long)M * N, S, stream);
+}
+
+// The same for more than 32 rows, same arguments. The binding has checked
+// 33 <= M, ((M - 1) * x_stride + K) * 2 < 2^31 (x is one buffer resource) and
+// ceil(M / 64) * ceil(N / 128) * S <= 2^23 (the grid).
+void kt_linear_w8_wide(const void* x, long x_stride, const void* wq,
+                       const void* scale, void* y, void* part, int M, int N,
+                       int K, int S, hipStream_t stream) {
+  const int kt = K / LW_KT;
+  const int tps = (kt + S - 1) / S;
+  const int mt = (M + LWW_BM - 1) / LWW_BM;
+  const dim3 grid((unsigned)((long)mt * ((N + LW_BN - 1) / LW_BN)),
+                  (unsigned)S);
+  hipLaunchKernelGGL(linear_w8_wide_kernel, grid, dim3(LW_THREADS), 0, stream,
+                     (const u16*)x, x_stride, (const unsigned char*)wq,
+                     (const float*)scale, (u16*)y,
+                     S > 1 ? (float*)part : (float*)nullptr, M, N, K, tps, mt);
+  if (S > 1) launch_reduce(part, y, (long)M * N, S, stream);
 }
 
 }  // extern "C"
